@@ -2,6 +2,7 @@
 """bench.py -- agent-env steps/s of the batched multi-UAV environment step on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 150 --warmup 30
+    python bench.py --gpus 1 --steps 150 --warmup 30 --full # and every other leg: steady state, roofline, COMA, CPU baseline, ...
     python bench.py --gpus 8 --steps 150 --warmup 30        # starts its own 8 ranks (one per GPU, RCCL) when not under a launcher
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 150 --warmup 30           # the same, under an external launcher
@@ -16,7 +17,19 @@ Default workload = BASELINE.json configs[1]: 4 UAVs, 256 x 256 grid, 1024 batche
 Inputs are synthetic and resident in HBM (truth fields generated on the device).  Envs are independent, so N GPUs
 shard envs with no data-path collective ("weak" scaling: 1024 envs per GPU).
 
-The JSON line also carries
+A plain run does only what the headline figure needs: set-up (placement search included), --warmup steps, the --steps timed
+steps, the outputs (--dump-outputs DIR) and the JSON line with metric, value, unit, higher_is_better, dtype, ms_per_step (one
+timed step), config (config.map_layout: the layout the timed envs used), placement, resets_timed, faults, cells and per_rank (every
+rank's own ms_per_step / rate / placement-search outcome; value_sum_of_ranks next to value_from_max_time).  Every other leg runs
+only under --full.
+
+--dump-outputs DIR writes what the timed loop's last step computed, taken right after that step (before a reset that follows it):
+  reward.npy [E, 2] (relative, absolute), positions.npy [E, N, 3], actions.npy [E, N], and the belief maps as row-major log-odds of
+  a fixed, seeded sample of the envs, local_maps_logodds.npy [S, N, gx, gy] and global_map_logodds.npy [S, gx, gy] (the env ids are
+  in the JSON line's `outputs`; at most 48 MiB of maps, where one env alone is larger a seeded sample of its cells).  All float32,
+  rank 0's envs.  The inputs depend on the arguments only, so two builds can be compared array for array.
+
+With --full the JSON line also carries
   roofline         : the map-update kernel K3 (k_sense_tiles): algorithmic bytes = 10 B per footprint cell (4R+4W posterior,
                      1R truth, 1W measurement code) / the kernel's own begin-to-end duration, taken from HIP
                      events bound to each dispatch (hipExtLaunchKernelGGL; what rocprofv3's kernel trace reports) over a
@@ -25,15 +38,15 @@ The JSON line also carries
                      step / ms_per_step / peak
   roofline_kernels : the same for the fusion launch (K4+K5: 8 B per cell of the union + 1 B per (cell, message)), the small
                      plan kernel, the reset kernels and, when training is on, the K6 feature builders
-  resets_timed, steady_state : how many episode resets the timed window held, and the same loop's rate over --steady-episodes (20)
-                     whole episodes right after it (exactly one reset per episode): the figure to quote for sustained throughput
-                     (also under roofline.steady_state, which the driver's record keeps)
+  steady_state     : the same loop's rate over --steady-episodes (20) whole episodes right after the timed window (exactly one
+                     reset per episode, where resets_timed says how many the timed window held): the figure to quote for sustained
+                     throughput (also under roofline.steady_state, which the driver's record keeps)
   roofline.batch_leg, config.map_layout : the same shape and loop at TWICE the batch (2048 envs by default; ten whole episodes; one GPU only), where
                      map_layout="auto" stores the maps as 128-byte tiles (ippm_set_map_layout: row-major rows get dearer per cell as a launch's maps
                      grow past ~2 GB, whole lines do not) -- NOT the metric's configuration, never `value`; and the layout the timed envs used
-  per_rank         : every rank's own ms_per_step / rate / placement-search outcome; value_sum_of_ranks next to value_from_max_time
-  ranks, rank_devices, collective : who took part (one entry per rank) and the gradient all-reduces RCCL carried in the
-                     COMA leg (backend, calls, bytes)
+  collective       : who took part in the COMA leg (one entry per rank) and the gradient all-reduces RCCL carried there
+                     (backend, calls, bytes)
+  coma_training, dropin_seam : COMA updates/s (--train-rounds) and the drop-in object surface's own rate (EpisodeGenerator.execute)
   cpu_baseline     : the NumPy oracle (a port of the reference's CPU path, parity-pinned against it) stepping the same
                      config on one host core (one env) and on all host cores (64 envs), bounded to ~10 s each; the
                      reference itself as probed in the build container is quoted as reference_probe
@@ -49,6 +62,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "ipp-marl_amd"))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
@@ -59,6 +73,25 @@ K3_LAYOUT_BYTES_PER_CELL = 8.375
 REFERENCE_PROBE = {"agent_env_steps_per_s": 10.0, "coma_updates_per_s": 0.164, "cores": 8,
                    "source": "SURVEY.md section 6: /root/reference run in the build container (default params, 493x493)"}
 PIXELS = {128: 15, 256: 30, 512: 60, 1024: 120}
+DUMP_MAP_BYTES = 48 << 20   # --dump-outputs: the sampled belief maps stay within this (all arrays together within 64 MB)
+
+
+def write_outputs(directory, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32; the two map arrays together within DUMP_MAP_BYTES (where even one
+    sampled env exceeds that, a fixed, seeded sample of each map array's cells, flattened).  -> {"dir", "arrays": {name: shape}}."""
+    os.makedirs(directory, exist_ok=True)
+    maps = [k for k in arrays if k.endswith("_logodds")]
+    map_bytes = sum(arrays[k].size * 4 for k in maps)
+    rng = np.random.default_rng(1)
+    shapes = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if name in maps and map_bytes > DUMP_MAP_BYTES:
+            keep = int(a.size * DUMP_MAP_BYTES // map_bytes)
+            a = a.reshape(-1)[np.unique(rng.integers(0, a.size, size=keep))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return {"dir": directory, "arrays": shapes}
 
 
 def bench_params(args):
@@ -293,7 +326,13 @@ def main():
                     "(roofline.batch_leg: where tile storage of the maps takes over from row-major rows)")
     ap.add_argument("--calib", action="store_true", help="PMC calibration: 3 device-to-device copies of the local maps (known "
                     "bytes read and written by a 16 B/lane streaming kernel) before the timed loop")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline figure: steady state, roofline leg and "
+                    "copy-rate yardstick, batch leg, COMA training, drop-in seam, CPU baseline (each with its own option above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32; maps of a fixed sample of envs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.streams <= 0:
         args.streams = 3 if (args.episode_comm_range or args.team_sizes) else 2
 
@@ -366,9 +405,10 @@ def main():
     # The roofline leg measures the kernels ONE LAUNCH AT A TIME at the full batch: with sub-batches on several streams that is a
     # second, whole-batch VecEnv (same config, same library, its own placement search), stepped on one stream after the timed loops.
     map_layout = "tiles: 128-byte tiles of 4 rows x 8 cells (ippm_set_map_layout)" if env.tiled else "rows: row-major [grid_x, grid_y]"
+    roofline_steps = args.roofline_steps if args.full else 0      # (the roofline leg is one of the --full legs)
     roof_env = VecEnv(params, args.envs, device=device, philox_seed=3, terrain=args.terrain, track_area=False, team_sizes=teams) \
-        if split and args.roofline_steps > 0 else env
-    first = roof_env if split and args.roofline_steps > 0 else (env.parts[0] if split else env)   # (copy-rate yardstick, PMC calibration)
+        if split and roofline_steps > 0 else env
+    first = roof_env if split and roofline_steps > 0 else (env.parts[0] if split else env)   # (copy-rate yardstick, PMC calibration)
     # where the allocator puts the maps is worth 10 % of the fusion kernel (VecEnv.tune_placement): a few candidate sets, one
     # episode each, before anything is timed
     placement = env.tune_placement(args.placement_draws)
@@ -417,7 +457,7 @@ def main():
         reset()
     if args.graphs:
         env.capture_step_graphs(POLICY_UNIFORM)
-    scratch = torch.empty_like(first.local)
+    scratch = torch.empty_like(first.local) if args.calib or args.full else None     # (marker copies, copy-rate yardstick)
 
     def stream_copy():
         first.ctx.call("ippm_stream_copy", first._p(first.local), _ffi.ptr(scratch), first.local.numel() * 4, first.stream)
@@ -427,6 +467,31 @@ def main():
         for _ in range(3):
             stream_copy()
         torch.cuda.synchronize()
+    # --dump-outputs: the last timed step's results are copied on each part's stream right after its step (a reset may follow it
+    # inside the same advance); the maps of a fixed, seeded sample of the envs only
+    dump = args.dump_outputs if rank == 0 else None
+    parts = env.parts if split else [env]
+    offsets = env.offsets if split else [0]
+    step_name = "step_graphed" if args.graphs else "steps"
+    captured = {}
+    if dump:
+        env_map_bytes = (N + 1) * env.d.grid_x * env.d.grid_y * 4
+        n_sample = min(E, max(1, DUMP_MAP_BYTES // env_map_bytes))
+        sample_envs = sorted(int(e) for e in np.random.default_rng(0).choice(E, size=n_sample, replace=False))
+        sample_rows = [torch.tensor([e - off for e in sample_envs if off <= e < off + part.E], dtype=torch.long, device=device)
+                       for part, off in zip(parts, offsets)]
+
+    def capture_after_step(k):
+        part = parts[k]
+        real = getattr(part, step_name)
+
+        def step(*a, **kw):
+            ret = real(*a, **kw)
+            captured[k] = {"reward": part.reward.clone(), "positions": part.pos.clone(), "actions": part.action.clone(),
+                           "local": part.local.index_select(0, sample_rows[k]), "glob": part.glob.index_select(0, sample_rows[k])}
+            return ret
+        setattr(part, step_name, step)      # (an instance attribute over the method, for the one step)
+
     run(args.warmup)
     env.counters(reset=True)
     torch.cuda.synchronize()
@@ -434,7 +499,15 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    resets_timed = run(args.steps)
+    if dump:
+        resets_timed = run(args.steps - 1)
+        for k in range(len(parts)):
+            capture_after_step(k)
+        resets_timed += run(1)
+        for part in parts:
+            delattr(part, step_name)
+    else:
+        resets_timed = run(args.steps)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -446,27 +519,38 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt[0])
     counters = env.counters()
-    # Steady state: the timed region above holds however many resets --steps happens to span (the driver's 20 steps: one, i.e. one
+    outputs = None
+    if dump:
+        def gather(key):
+            return torch.cat([captured[k][key] for k in range(len(parts))])
+        outputs = write_outputs(dump, {"reward": gather("reward").cpu().numpy(), "positions": gather("positions").cpu().numpy(),
+                                       "actions": gather("actions").cpu().numpy(),
+                                       "local_maps_logodds": env.rows_view(gather("local")).cpu().numpy(),
+                                       "global_map_logodds": env.rows_view(gather("glob")).cpu().numpy()})
+        outputs["sample_envs"] = sample_envs
+        captured.clear()
+    # Steady state (--full): the timed region above holds however many resets --steps happens to span (the driver's 20 steps: one, i.e. one
     # per 20 steps where an episode has one per 16); any window of whole episodes holds exactly one reset per episode whatever its
     # phase, so the loop simply goes on for --steady-episodes (20) more episodes' worth of steps under the same barrier / max-over-ranks clock.
-    ss_steps, ss_resets = args.steady_episodes * T, 0
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    s0 = time.perf_counter()
-    ss_resets = run(ss_steps)
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    ss_dt = time.perf_counter() - s0
-    if dist:
-        tt = torch.tensor([ss_dt], dtype=torch.float64, device=device)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        ss_dt = float(tt[0])
-    after_ss = env.counters()
-    ss_counters = {k: after_ss[k] - counters[k] for k in counters}      # the steady-state leg's own cells
+    if args.full:
+        ss_steps, ss_resets = args.steady_episodes * T, 0
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        s0 = time.perf_counter()
+        ss_resets = run(ss_steps)
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        ss_dt = time.perf_counter() - s0
+        if dist:
+            tt = torch.tensor([ss_dt], dtype=torch.float64, device=device)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            ss_dt = float(tt[0])
+        after_ss = env.counters()
+        ss_counters = {k: after_ss[k] - counters[k] for k in counters}      # the steady-state leg's own cells
     faults = int(env.fault.abs().sum())        # (SplitVecEnv: joins its streams first)
     grid = [env.d.grid_x, env.d.grid_y]
 
@@ -475,7 +559,7 @@ def main():
     # rocprofv3's kernel trace reports; no barrier packets, nothing to calibrate away) -- and with its own work counters, so
     # bytes and durations cover exactly the same launches whatever --steps was.
     times, rl_counters, rl_resets, overlapped = {}, None, 0, None
-    if args.roofline_steps > 0 and not args.graphs:
+    if roofline_steps > 0 and not args.graphs:     # (roofline_steps: 0 without --full)
         if split:
             # With sub-batches on several streams a kernel's begin-to-end time in the loops above includes what the other streams'
             # kernels took from it.  First a short stretch of that loop with the events on (`overlapped_us`: what a sub-batch's kernels
@@ -508,10 +592,10 @@ def main():
         roof_env.counters(reset=True)
         roof_env.profile = True
         if roof_env is env:
-            rl_resets = run(args.roofline_steps)
+            rl_resets = run(roofline_steps)
         else:
             t_leg = 0
-            for _ in range(args.roofline_steps):
+            for _ in range(roofline_steps):
                 roof_env.steps(t_leg, policy=POLICY_UNIFORM, features=False)
                 t_leg += 1
                 if t_leg == T:
@@ -521,20 +605,21 @@ def main():
         roof_env.profile = False
         times = roof_env.event_times_us()
         rl_counters = roof_env.counters()
-    # second denominator: what a plain 16 B/lane device-to-device copy of the local maps reaches on this box
-    stream_copy()
-    ca, cb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ca.record()
-    for _ in range(3):
-        stream_copy()
-    cb.record()
-    torch.cuda.synchronize()
-    copy_gbs = 3 * 2 * first.local.numel() * 4 / (ca.elapsed_time(cb) * 1e-3) / 1e9
-    del scratch
-    launch_envs = roof_env.E if args.roofline_steps > 0 else first.E     # envs per kernel launch of the roofline leg
+    launch_envs = roof_env.E if roofline_steps > 0 else first.E     # envs per kernel launch of the roofline leg
     sub_envs = env.sizes[0] if split else E                              # envs per kernel launch of the timed loops
-    pmc, pmc_path = newest_pmc_summary(E, N, grid[0], launch_envs)
-    pmc_ok = bool(pmc) and not teams and args.comm_range is None     # (counter passes of this command at this shape and workload)
+    if args.full:
+        # second denominator: what a plain 16 B/lane device-to-device copy of the local maps reaches on this box
+        stream_copy()
+        ca, cb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ca.record()
+        for _ in range(3):
+            stream_copy()
+        cb.record()
+        torch.cuda.synchronize()
+        copy_gbs = 3 * 2 * first.local.numel() * 4 / (ca.elapsed_time(cb) * 1e-3) / 1e9
+        pmc, pmc_path = newest_pmc_summary(E, N, grid[0], launch_envs)
+        pmc_ok = bool(pmc) and not teams and args.comm_range is None     # (counter passes of this command at this shape and workload)
+    del scratch
 
     TIMING = ("HIP start/stop events bound to each dispatch (hipExtLaunchKernelGGL): the kernel's own begin-to-end duration, as "
               "rocprofv3's kernel trace reports it; no bracket overhead to subtract, so frac_raw == frac")
@@ -573,7 +658,7 @@ def main():
         roofline = roofline_entry("k_sense_update", "K3: sense + Bayes update of the footprint tiles", K3_BYTES_PER_CELL * cells, k3,
                                   {"algorithmic_bytes_per_cell": K3_BYTES_PER_CELL, "cells_per_launch": cells,
                                    "launch_envs": launch_envs,
-                                   "launches": f"the K3 launches of {args.roofline_steps} steps ({rl_resets} resets among them) right after "
+                                   "launches": f"the K3 launches of {roofline_steps} steps ({rl_resets} resets among them) right after "
                                                "the timed region" + (f": the whole batch of {launch_envs} envs per launch on one stream, every launch alone "
                                                f"on the device (a second VecEnv of the same config); the timed region steps {args.streams} sub-batches of "
                                                f"{sub_envs} envs on {args.streams} streams, whose kernels run side by side: overlapped_us = their "
@@ -613,13 +698,13 @@ def main():
             if cls in times:
                 roofline_kernels.append({"kernel": times[cls]["kernel"], "what": what, "avg_launch_us": times[cls]["avg_us"],
                                          "min_launch_us": times[cls]["min_us"], "timed_launches": times[cls]["launches"],
-                                         "us_per_step": times[cls]["avg_us"] * times[cls]["launches"] / args.roofline_steps})
+                                         "us_per_step": times[cls]["avg_us"] * times[cls]["launches"] / roofline_steps})
 
     # Batch leg: the same shape at TWICE the metric's batch (config 2: 2048 envs).  Row-major rows get dearer per cell as a launch's maps grow, the
     # 128-byte tiles of ippm_set_map_layout do not, and map_layout="auto" takes them from 2 GB of maps on -- so the chip has more to give than the
     # metric's 1024 envs show.  NOT the metric's configuration: reported beside it under roofline.batch_leg, never as `value`.
     batch_leg = None
-    if args.batch_leg and world == 1 and not args.graphs and not teams:
+    if args.full and args.batch_leg and world == 1 and not args.graphs and not teams:
         try:
             env = roof_env = first = None
             torch.cuda.empty_cache()
@@ -664,7 +749,7 @@ def main():
     if batch_leg is not None and isinstance(roofline, dict):
         roofline["batch_leg"] = batch_leg
     coma = collective = None
-    if args.train_rounds > 0:
+    if args.full and args.train_rounds > 0:
         # BASELINE configs[2]: full COMA actor + counterfactual critic training on the same env config
         from ippmarl.trainer import COMATrainer
         env = roof_env = first = None  # release the env-only state before the trainer allocates its own
@@ -724,9 +809,9 @@ def main():
                 "tracked_us": {k: kt[k]["avg_us"] for k in ("sense", "fuse") if k in kt},
                 "untracked_us": untracked,
                 "cells_per_step": {"tracked_rollout": coma["rollout_kernel_us"]["cells_per_step"],
-                                   "untracked_env_only": ({"sense": rl_counters["sense_cells"] / args.roofline_steps,
-                                                           "fuse_local": rl_counters["fuse_local_cells"] / args.roofline_steps,
-                                                           "fuse_global": rl_counters["fuse_global_cells"] / args.roofline_steps}
+                                   "untracked_env_only": ({"sense": rl_counters["sense_cells"] / roofline_steps,
+                                                           "fuse_local": rl_counters["fuse_local_cells"] / roofline_steps,
+                                                           "fuse_global": rl_counters["fuse_global_cells"] / roofline_steps}
                                                           if rl_counters else None)},
                 "streaming_form_bytes_per_step": 4.0 * (N + 1) * grid[0] * grid[1] * E})
         if world > 1:   # evidence that the gradient exchange really ran over `world` ranks: every rank's device, calls and bytes
@@ -777,7 +862,7 @@ def main():
                                              "adam_steps_per_update": stats["adam_steps"],
                                              "hip_graphs": "16 rollout-step graphs + 1 update graph per round (COMATrainer.capture_graphs)"}
     seam = None
-    if rank == 0 and not args.no_dropin_seam and not teams:
+    if args.full and rank == 0 and not args.no_dropin_seam and not teams:
         env = roof_env = first = None
         torch.cuda.empty_cache()
         seam = dropin_seam(device)
@@ -811,7 +896,7 @@ def main():
                        "episode_steps": T, "terrain": args.terrain, "parallelism": f"env-sharded x{world} (no data-path collective)",
                        "streams": args.streams if split else 1, "staggered_episodes": bool(split and args.stagger), "envs_per_launch": sub_envs,
                        "launches_per_step": 3 * (args.streams if split else 1), "stream_check": stream_check, "hip_graphs": bool(args.graphs),
-                       "roofline_steps": args.roofline_steps,
+                       "roofline_steps": roofline_steps, "full": bool(args.full),
                        "map_layout": map_layout,
                        "terrain_prefetch": bool(args.terrain_prefetch and args.terrain == "random_field")},
             "ranks": world,
@@ -820,7 +905,7 @@ def main():
                              "note": f"the same loop continued for {ss_steps} steps = {ss_steps // T} whole episodes (exactly one reset per {T} steps, as in an "
                                      f"endless run); `value` above is the driver's window of --steps {args.steps}, which held {resets_timed} reset(s), "
                                      f"i.e. one per {args.steps / max(resets_timed, 1):.1f} steps" + ("" if resets_timed else " (none at all)")
-                                     + ": quote steady_state for sustained throughput"},
+                                     + ": quote steady_state for sustained throughput"} if args.full else None,
             "per_rank": {"ranks": per_rank, "slowest_rank": max(per_rank, key=lambda r: r["ms_per_step"])["rank"],
                          "ms_per_step_min": min(r["ms_per_step"] for r in per_rank), "ms_per_step_max": max(r["ms_per_step"] for r in per_rank),
                          "value_sum_of_ranks": sum(r["agent_env_steps_per_s"] for r in per_rank), "value_from_max_time": total_steps / dt},
@@ -833,11 +918,16 @@ def main():
             "coma_training": coma,
             "dropin_seam": seam,
         }
+        if not args.full:     # (legs that did not run leave no entry)
+            for key in ("steady_state", "collective", "roofline", "roofline_kernels", "roofline_leg_placement", "coma_training", "dropin_seam"):
+                del out[key]
+        if outputs:
+            out["outputs"] = outputs
     if dist:   # every collective is done: the other ranks may leave while rank 0 times the CPU baseline on the host cores
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
 

@@ -1053,3 +1053,51 @@ def test_kernel_timing_reports_dispatch_durations():
     times = env.event_times_us()
     assert times["reset_maps"]["launches"] == 1 and times["reset_maps"]["kernel"] == "k_reset_maps"
     assert times["reset"]["launches"] == 2 and times["reset"]["kernel"] == "k_fill_truth"   # scalars, then the half-plane truth (the last one names the class)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """bench.py at a small batch: a plain run times exactly --steps steps and carries none of the --full legs; --dump-outputs holds the
+    last timed step's results -- here the step that ends an episode, taken before the reset that follows it -- identical in another
+    process and on one stream instead of two, and equal to a VecEnv stepped the same way here; --full adds the legs."""
+    import argparse
+    import json
+    import subprocess
+    import sys
+    import bench
+    from ippmarl.parallel import episode_ids
+    from ippmarl.vec_env import POLICY_UNIFORM
+
+    def line(*extra):
+        out = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--envs", "8", "--steps", "5", "--warmup", "10", *extra],
+                             capture_output=True, text=True, timeout=600, cwd=bench.ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+
+    def load(d):
+        return {k: np.load(os.path.join(d, f"{k}.npy")) for k in ("reward", "positions", "actions", "local_maps_logodds", "global_map_logodds")}
+
+    rec = line("--dump-outputs", str(tmp_path / "a"))
+    assert rec["steps"] == 5 and rec["ms_per_step"] > 0 and rec["faults"] == 0 and rec["config"]["full"] is False
+    assert {"metric", "value", "unit", "higher_is_better", "dtype"} <= set(rec)
+    assert not {"steady_state", "roofline", "roofline_kernels", "coma_training", "dropin_seam", "cpu_baseline"} & set(rec)
+    a = load(tmp_path / "a")
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    line("--dump-outputs", str(tmp_path / "b"))
+    line("--streams", "1", "--dump-outputs", str(tmp_path / "c"))
+    for other in (load(tmp_path / "b"), load(tmp_path / "c")):
+        for k in a:
+            assert np.array_equal(a[k], other[k]), k
+    # the same 15 steps (10 warm-up + 5 timed: one whole episode) on a VecEnv of this process
+    params = bench.bench_params(argparse.Namespace(grid=256, agents=4, actions=None, episode_comm_range=False, comm_range=None))
+    env = _env(params, 8, philox_seed=3, terrain="random_field", track_area=False)
+    env.reset(episode_ids(1, 0, 8, 0, 1))
+    for t in range(env.d.budget + 1):
+        env.steps(t, policy=POLICY_UNIFORM, features=False)
+    sample = rec["outputs"]["sample_envs"]
+    assert np.array_equal(a["reward"], env.reward.cpu().numpy())
+    assert np.array_equal(a["positions"], env.pos.cpu().numpy()) and np.array_equal(a["actions"], env.action.cpu().numpy())
+    assert np.array_equal(a["local_maps_logodds"], env.rows_view(env.local)[sample].cpu().numpy())
+    assert np.array_equal(a["global_map_logodds"], env.rows_view(env.glob)[sample].cpu().numpy())
+    full = line("--full", "--no-cpu-baseline", "--train-rounds", "0", "--no-dropin-seam", "--no-batch-leg", "--roofline-steps", "15",
+                "--steady-episodes", "1")
+    assert full["config"]["full"] is True and full["steady_state"]["steps"] == 15 and full["roofline"]["timed_launches"] > 0

@@ -166,6 +166,34 @@ def test_launcher_retries_once_with_the_other_ipc_setting(monkeypatch):
     assert [c[1] for c in calls] == ["unset", "0"]
 
 
+def test_bench_output_writer(tmp_path):
+    """bench.write_outputs (--dump-outputs): float32 .npy files; map arrays within DUMP_MAP_BYTES by a seeded sample of their cells
+    where even one env is larger, the same sample every time; and the options --full / --dump-outputs exist."""
+    import subprocess
+    import sys
+    import bench
+    rng = np.random.default_rng(5)
+    small = {"reward": rng.random((64, 2)), "positions": rng.integers(0, 40, (64, 4, 3)),
+             "local_maps_logodds": rng.random((3, 4, 64, 64)), "global_map_logodds": rng.random((3, 64, 64))}
+    rec = bench.write_outputs(str(tmp_path / "a"), small)
+    assert rec["arrays"] == {k: list(v.shape) for k, v in small.items()}
+    for k, v in small.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    g = 1024      # one env of 16 UAVs on a 1024^2 grid: 68 MB of maps
+    big = {"local_maps_logodds": np.ones((1, 16, g, g), dtype=np.float32), "global_map_logodds": np.ones((1, g, g), dtype=np.float32)}
+    big["local_maps_logodds"].reshape(-1)[:: 997] = np.arange(big["local_maps_logodds"].size // 997 + 1) % 251
+    first = bench.write_outputs(str(tmp_path / "b"), big)
+    again = bench.write_outputs(str(tmp_path / "c"), big)
+    assert first["arrays"] == again["arrays"]
+    sizes = [os.path.getsize(tmp_path / "b" / f"{k}.npy") for k in big]
+    assert sum(sizes) <= bench.DUMP_MAP_BYTES + 4096 and min(sizes) > 0
+    for k in big:
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy"))
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
 def test_fusion_rotation_rule_spreads_every_env_over_all_xcds():
     """The launch rule of the tile fusion and of the row walker's work-list form (fuse_tiles.hip, fuse.hip), restated: workgroup
     (x, f) of a grid (E, per_env) is linear workgroup x + E * f and runs on XCD (x + E * f) % 8; it serves env

@@ -6,7 +6,7 @@ for rep in $(seq 1 ${REPS:-2}); do
 for item in "$@"; do
   IFS=: read name lib tiled <<< "$item"
   LIB=$PWD/ipp-marl_amd/lib/libippmarl.so; [ "$lib" != "-" ] && LIB=$PWD/ipp-marl_amd/lib/libippmarl_$lib.so
-  IPPMARL_LIB=$LIB IPPM_MAP_TILED=$tiled timeout 300 python bench.py --steps ${STEPS:-60} --warmup 15 --no-cpu-baseline --train-rounds 0 --no-dropin-seam --steady-episodes ${STEADY:-3} ${BENCH_ARGS} > $OUT/bench_${name}_$rep.json 2> $OUT/bench_${name}_$rep.err
+  IPPMARL_LIB=$LIB IPPM_MAP_TILED=$tiled timeout 300 python bench.py --full --steps ${STEPS:-60} --warmup 15 --no-cpu-baseline --train-rounds 0 --no-dropin-seam --steady-episodes ${STEADY:-3} ${BENCH_ARGS} > $OUT/bench_${name}_$rep.json 2> $OUT/bench_${name}_$rep.err
   python - <<PY
 import json
 try:

@@ -3,7 +3,7 @@
 TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for a in "$@"; do
-  timeout 300 python bench.py --steps ${STEPS:-60} --warmup 15 --no-cpu-baseline --train-rounds 0 --no-dropin-seam --steady-episodes 3 $a > $OUT/b.json 2> $OUT/b.err
+  timeout 300 python bench.py --full --steps ${STEPS:-60} --warmup 15 --no-cpu-baseline --train-rounds 0 --no-dropin-seam --steady-episodes 3 $a > $OUT/b.json 2> $OUT/b.err
   python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ for cfg in "$@"; do
   name=$(echo $cfg | tr '=,' '__')
   envs=$(echo $cfg | tr ',' ' ')
   [ "$cfg" = "-" ] && envs=""
-  env $envs timeout 300 python bench.py --steps 60 --warmup 15 --no-cpu-baseline --train-rounds ${TRAIN_ROUNDS:-0} ${BENCH_ARGS} > $OUT/bench_$name.json 2> $OUT/bench_$name.err
+  env $envs timeout 300 python bench.py --full --steps 60 --warmup 15 --no-cpu-baseline --train-rounds ${TRAIN_ROUNDS:-0} ${BENCH_ARGS} > $OUT/bench_$name.json 2> $OUT/bench_$name.err
   python - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-r6_c4}; mkdir -p $OUT
 B="--envs 1024 --agents 8 --grid 512 --steps 16 --warmup 16 --train-rounds 0 --no-cpu-baseline --no-dropin-seam --steady-episodes 1 --streams 1 --placement-draws ${DRAWS:-8} --roofline-steps 45"
 run() {   # $1 label, rest: env assignments
   label=$1; shift
-  env "$@" timeout 400 python bench.py $B > $OUT/c4.json 2> $OUT/c4.err || tail -3 $OUT/c4.err
+  env "$@" timeout 400 python bench.py --full $B > $OUT/c4.json 2> $OUT/c4.err || tail -3 $OUT/c4.err
   python - "$label" <<PY
 import json,sys
 d=json.loads([l for l in open("$OUT/c4.json") if l.startswith("{")][-1])

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 timeout 600 python -m pytest tests -m gpu -q -x --timeout 300 > $OUT/pytest.log 2>&1
 echo "pytest rc=$?" >> $OUT/pytest.log
 tail -15 $OUT/pytest.log
-timeout 300 python bench.py --steps 60 --warmup 15 --no-cpu-baseline --train-rounds ${TRAIN_ROUNDS:-1} > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --full --steps 60 --warmup 15 --no-cpu-baseline --train-rounds ${TRAIN_ROUNDS:-1} > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?"; tail -3 $OUT/bench.err; python - <<PY
 import json
 try:

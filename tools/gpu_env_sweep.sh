@@ -4,7 +4,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for cfg in "$@"; do
   envs=$(echo $cfg | tr ',' ' '); [ "$cfg" = "-" ] && envs=""
-  env $envs timeout 300 python bench.py --steps ${STEPS:-30} --warmup 15 --no-cpu-baseline --train-rounds 0 --no-dropin-seam --steady-episodes 2 ${BENCH_ARGS} > $OUT/b.json 2> $OUT/b.err
+  env $envs timeout 300 python bench.py --full --steps ${STEPS:-30} --warmup 15 --no-cpu-baseline --train-rounds 0 --no-dropin-seam --steady-episodes 2 ${BENCH_ARGS} > $OUT/b.json 2> $OUT/b.err
   python - <<PY
 import json
 try:

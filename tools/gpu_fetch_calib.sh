@@ -25,7 +25,7 @@ rm -rf $OUT/cal1 $OUT/cal2 $OUT/cal3
 B="--steps 30 --warmup 15 --train-rounds 0 --no-cpu-baseline --no-dropin-seam --steady-episodes 2 --roofline-steps 90"
 for rep in 1 2 3; do
   for lib in libippmarl.so libippmarl_alignfp.so; do
-    IPPMARL_LIB=$PWD/ipp-marl_amd/lib/$lib timeout 300 python bench.py $B > $OUT/ab.json 2> $OUT/ab.err || tail -3 $OUT/ab.err
+    IPPMARL_LIB=$PWD/ipp-marl_amd/lib/$lib timeout 300 python bench.py --full $B > $OUT/ab.json 2> $OUT/ab.err || tail -3 $OUT/ab.err
     python - $lib <<PY
 import json,sys
 d=json.loads([l for l in open("$OUT/ab.json") if l.startswith("{")][-1])

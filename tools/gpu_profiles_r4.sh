@@ -6,7 +6,7 @@
 TAG=${1:-prof4}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-BENCH="python bench.py --steps 60 --warmup 15 --no-cpu-baseline --train-rounds 0 --calib ${BENCH_ARGS}"
+BENCH="python bench.py --full --steps 60 --warmup 15 --no-cpu-baseline --train-rounds 0 --calib ${BENCH_ARGS}"
 timeout -k 10 ${PROF_TIMEOUT:-300} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o p -- $BENCH > $OUT/bench_under_rocprofv3.json 2> $OUT/stats.err
 find $OUT/stats -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_whole_process.csv \;
 # (bench.py --streams 2, the default: kernel_stats_bench_loop.csv = the roofline leg, the whole batch per launch, every launch alone;

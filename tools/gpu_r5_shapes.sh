@@ -13,8 +13,8 @@ SQ2="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_A
 shape() {   # name, E, N, G, bench args
   local name=$1 E=$2 N=$3 G=$4; shift 4
   local ARGS="$*"
-  local LINE="python bench.py $ARGS --steps 30 --warmup 15 --no-cpu-baseline --train-rounds 0"
-  local SHORT="python bench.py $ARGS --steps 16 --warmup 16 --no-cpu-baseline --train-rounds 0 --roofline-steps 16 --placement-draws 1 --calib"
+  local LINE="python bench.py --full $ARGS --steps 30 --warmup 15 --no-cpu-baseline --train-rounds 0"
+  local SHORT="python bench.py --full $ARGS --steps 16 --warmup 16 --no-cpu-baseline --train-rounds 0 --roofline-steps 16 --placement-draws 1 --calib"
   echo "=== $name: $ARGS"
   if [ -z "$SQ_ONLY" ]; then
   timeout 600 $LINE > $OUT/bench_$name.json 2> $OUT/bench_$name.err

@@ -8,6 +8,6 @@ timeout 400 python tools/learning_curve.py --envs 1024 --updates 40 --eval-every
 tail -1 $OUT/lc_1024_fixed.log
 timeout 400 python tools/learning_curve.py --envs 5 --graphs --eval-envs 256 --updates 1500 --eval-every 150 --no-ig --out $OUT/lc_5_reference.json > $OUT/lc_5_reference.log 2>&1
 tail -1 $OUT/lc_5_reference.log
-timeout 600 python bench.py --steps 150 --warmup 30 --train-rounds 1 > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 150 --warmup 30 --train-rounds 1 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?"; tail -3 $OUT/bench.err
 python tools/bench_brief.py $OUT/bench.json

@@ -4,7 +4,7 @@
 TAG=${1:-r6last}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 bash tools/gpu_profiles_r4.sh $TAG > $OUT/profiles.log 2>&1; tail -30 $OUT/profiles.log | cut -c1-220
-timeout 900 python bench.py --gpus 8 --dist-backend gloo --envs 64 --steps 30 --warmup 10 --train-rounds 1 --no-cpu-baseline --no-dropin-seam > $OUT/bench_gpus8_gloo_one_gpu.json 2> $OUT/g8.err
+timeout 900 python bench.py --full --gpus 8 --dist-backend gloo --envs 64 --steps 30 --warmup 10 --train-rounds 1 --no-cpu-baseline --no-dropin-seam > $OUT/bench_gpus8_gloo_one_gpu.json 2> $OUT/g8.err
 echo "rc=$? $(tail -2 $OUT/g8.err | cut -c1-300)"
 python - <<PY
 import json

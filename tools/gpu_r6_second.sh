@@ -13,7 +13,7 @@ done
 B="--steps 150 --warmup 30 --train-rounds 0 --no-cpu-baseline --no-dropin-seam --roofline-steps 0"
 for rep in 1 2; do
   for v in "--streams 2" "--streams 3" "--streams 2 --no-stagger" "--streams 3 --no-stagger" "--streams 4"; do
-    timeout 200 python bench.py $B $v > $OUT/b.json 2> $OUT/b.err || tail -3 $OUT/b.err
+    timeout 200 python bench.py --full $B $v > $OUT/b.json 2> $OUT/b.err || tail -3 $OUT/b.err
     python - "$v" <<PY
 import json,sys
 d=json.loads([l for l in open("$OUT/b.json") if l.startswith("{")][-1])

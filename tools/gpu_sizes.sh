@@ -3,7 +3,7 @@
 TAG=$1; OUT=gpurun_out/$TAG; mkdir -p $OUT
 for spec in "--envs 256" "--envs 512" "--envs 2048" "--envs 1024 --agents 8 --grid 512" "--envs 1024 --grid 1024" "--envs 512 --agents 8 --grid 1024" "--envs 256 --graphs 1"; do
   name=$(echo $spec | tr -d '-' | tr ' ' '_')
-  timeout 300 python bench.py --steps 60 --warmup 15 --no-cpu-baseline --train-rounds 0 $spec > $OUT/b_$name.json 2> $OUT/b_$name.err
+  timeout 300 python bench.py --full --steps 60 --warmup 15 --no-cpu-baseline --train-rounds 0 $spec > $OUT/b_$name.json 2> $OUT/b_$name.err
   python - <<PY
 import json
 try:

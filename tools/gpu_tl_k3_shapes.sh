@@ -3,7 +3,7 @@
 OUT=gpurun_out/${1:-tl6}; mkdir -p $OUT
 for cfg in ${CFGS:-"0 2 2 1" "1 2 2 1" "1 2 2 0" "1 4 3 0" "1 2 3 0" "1 1 4 0" "1 2 4 0" "1 4 2 0" "1 1 3 0" "1 4 4 0"}; do
   set -- $(echo $cfg | tr ',' ' ')
-  IPPM_MAP_TILED=$1 IPPM_K3_WPG=$2 IPPM_K3_CHN=$3 IPPM_K3_GO=$4 timeout 300 python bench.py --steps ${STEPS:-45} --warmup 15 --no-cpu-baseline --train-rounds 0 --no-dropin-seam --steady-episodes 2 ${BENCH_ARGS} > $OUT/b.json 2> $OUT/b.err
+  IPPM_MAP_TILED=$1 IPPM_K3_WPG=$2 IPPM_K3_CHN=$3 IPPM_K3_GO=$4 timeout 300 python bench.py --full --steps ${STEPS:-45} --warmup 15 --no-cpu-baseline --train-rounds 0 --no-dropin-seam --steady-episodes 2 ${BENCH_ARGS} > $OUT/b.json 2> $OUT/b.err
   python - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 # the COMA leg's rollout kernels (tracked area sums) under either map layout at a batch where "auto" takes tiles: $1 = tag, BENCH_ARGS = shape
 OUT=gpurun_out/${1:-trl}; mkdir -p $OUT
 for tiled in 0 1 0 1; do
-  IPPM_MAP_TILED=$tiled timeout 600 python bench.py ${BENCH_ARGS:---envs 2048} --steps 15 --warmup 15 --no-cpu-baseline --no-dropin-seam --no-batch-leg --steady-episodes 1 --roofline-steps 0 --train-rounds 1 > $OUT/b.json 2> $OUT/b.err
+  IPPM_MAP_TILED=$tiled timeout 600 python bench.py --full ${BENCH_ARGS:---envs 2048} --steps 15 --warmup 15 --no-cpu-baseline --no-dropin-seam --no-batch-leg --steady-episodes 1 --roofline-steps 0 --train-rounds 1 > $OUT/b.json 2> $OUT/b.err
   python - <<PY
 import json
 try:

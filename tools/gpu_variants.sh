@@ -7,7 +7,7 @@ for spec in "$@"; do
   lib=""; [ "$var" != "-" ] && lib="IPPMARL_LIB=$PWD/ipp-marl_amd/lib/libippmarl_$var.so"
   envs=$(echo $cfg | tr ',' ' ')
   name=$(echo ${var}_$cfg | tr '=,' '__')
-  env $lib $envs timeout 300 python bench.py --steps 60 --warmup 15 --no-cpu-baseline --train-rounds ${TRAIN_ROUNDS:-0} ${BENCH_ARGS} > $OUT/bench_$name.json 2> $OUT/bench_$name.err
+  env $lib $envs timeout 300 python bench.py --full --steps 60 --warmup 15 --no-cpu-baseline --train-rounds ${TRAIN_ROUNDS:-0} ${BENCH_ARGS} > $OUT/bench_$name.json 2> $OUT/bench_$name.err
   python - <<PY
 import json
 try:

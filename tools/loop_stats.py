@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-kernel durations of the bench LOOP from rocprofv3's per-dispatch kernel trace (csv) of `bench.py --calib`: only the
+"""Per-kernel durations of the bench LOOP from rocprofv3's per-dispatch kernel trace (csv) of `bench.py --full --calib`: only the
 dispatches between the three k_stream_copy launches of bench.py --calib (right before its warm-up loop, i.e. after
 VecEnv.tune_placement's episodes on candidate allocations) and the copy-rate yardstick that follows the roofline leg: warm-up,
 timed loop and roofline leg, the launches whose durations bench.py's own roofline entries report.
@@ -12,7 +12,7 @@ df = pd.read_csv(sys.argv[1]).sort_values("Start_Timestamp").reset_index(drop=Tr
 is_copy = df["Kernel_Name"].str.contains("k_stream_copy").to_numpy()
 start = next((i + 3 for i in range(len(df) - 2) if is_copy[i] and is_copy[i + 1] and is_copy[i + 2]), None)
 if start is None:
-    raise SystemExit("no run of three k_stream_copy launches in the trace (run bench.py with --calib)")
+    raise SystemExit("no run of three k_stream_copy launches in the trace (run bench.py with --full --calib)")
 end = next((i for i in range(start, len(df)) if is_copy[i]), len(df))   # the next marker: the roofline leg's (--streams > 1) or the yardstick
 
 

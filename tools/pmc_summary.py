@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""profiles/rNN/pmc_summary.json from rocprofv3's sqlite output of three runs of `bench.py --calib`:
+"""profiles/rNN/pmc_summary.json from rocprofv3's sqlite output of three runs of `bench.py --full --calib`:
 a FETCH_SIZE pass, a WRITE_SIZE pass (each `--pmc X --kernel-trace` only) and a plain `--kernel-trace` run for durations.
 
 HBM bytes follow /opt/skills/guides/MI355X_MICROARCH.md (HBM section): FETCH_SIZE / WRITE_SIZE count in KiB; on gfx950

@@ -15,7 +15,7 @@ df["k"] = df[name].str.replace("void ", "").str.slice(0, 44)
 g = df.groupby(["k", grid])["us"].agg(["count", "mean", "min", "max", "sum"]).sort_values("sum", ascending=False)
 print(g[g["sum"] > (float(sys.argv[2]) if len(sys.argv) > 2 else 50)].round(1).to_string())
 
-# (bench.py --calib brackets its loops between three k_stream_copy launches and the copy-rate yardstick at the end: only what
+# (bench.py --full --calib brackets its loops between three k_stream_copy launches and the copy-rate yardstick at the end: only what
 #  lies between them is the bench loop -- the placement search runs before, the COMA leg after)
 copies = df.sort_values("start").reset_index(drop=True)
 is_copy = copies["k"].str.contains("k_stream_copy").to_numpy()
