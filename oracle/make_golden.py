@@ -219,6 +219,102 @@ def gen_masks():
     save("masks", **out)
 
 
+# ------------------------------------------------------------------ 5b: rectangular worlds (x_dim != y_dim)
+# (params set, x_dim, y_dim) -> grid_x x grid_y: the rectangular shapes of tests/test_rect_grids.py
+RECT_SETS = [("small", 50, 100), ("small", 100, 50), ("small", 50, 200), ("small", 200, 50), ("c2", 25, 200), ("c2", 200, 25),
+             ("c2", 50, 250), ("c4", 25, 50), ("small", 75, 50), ("small", 45, 50), ("small", 50, 45), ("c2", 35, 50)]
+
+
+def rect_key(name, x, y):
+    return f"{name}_{x}x{y}"
+
+
+def gen_rect_geometry():
+    """Grid dims and resolution, lattice, start states, footprints and action / collision masks of the reference on rectangular
+    worlds, where every quantity that has an x and a y differs between the axes."""
+    rng = np.random.RandomState(29)
+    out = {}
+    for name, xm, ym in RECT_SETS:
+        k = rect_key(name, xm, ym)
+        p = make_params(name, environment__x_dim=xm, environment__y_dim=ym)
+        gm = GridMap(p)
+        ss = AgentStateSpace(p)
+        cam = Camera(p, AltitudeSensorModel(p), gm)
+        out[f"{k}_res"] = np.array([gm.resolution_x, gm.resolution_y])
+        out[f"{k}_dims"] = np.array([gm.x_dim, gm.y_dim])
+        out[f"{k}_space"] = np.array(ss.space_dim)
+        out[f"{k}_starts"] = np.array([[ss.get_random_agent_state(a, e) for a in range(16)] for e in range(1, 33)], dtype=np.int32)
+        full, clip, fixed, lattice = [], [], [], []
+        for x in range(ss.space_x_dim):
+            for y in range(ss.space_y_dim):
+                for z in range(ss.space_z_dim):
+                    pos = ss.index_to_position([x, y, z])
+                    f, c = cam.project_field_of_view(pos, gm.resolution_x, gm.resolution_y)
+                    full.append(f)
+                    clip.append(c)
+                    fixed.append(get_fixed_footprint_coordinates(f, c))
+                    lattice.append(pos)
+        out[f"{k}_fp_full"] = np.array(full, dtype=np.int32)
+        out[f"{k}_fp_clip"] = np.array(clip, dtype=np.int32)
+        out[f"{k}_fp_fixed"] = np.array(fixed, dtype=np.int32)
+        for A in (6, 27):
+            pa = make_params(name, environment__x_dim=xm, environment__y_dim=ym, experiment__constraints__num_actions=A)
+            asp = AgentActionSpace(pa)
+            out[f"{k}_a{A}_mask"] = np.array([np.asarray(asp.get_action_mask(pos)[0]) for pos in lattice], dtype=np.uint8)
+            # collision cases near the four borders: own position within two lattice steps of one border, 1-3 already-moved others
+            # within two steps of it
+            sx, sy, sz = ss.space_x_dim, ss.space_y_dim, ss.space_z_dim
+            cp, co, cn, cm_in, cm_out = [], [], [], [], []
+            for case in range(96):
+                ix = np.array([rng.randint(0, sx), rng.randint(0, sy)])
+                side = case % 4
+                ix[side // 2] = rng.randint(0, 2) if side % 2 == 0 else (sx, sy)[side // 2] - 1 - rng.randint(0, 2)
+                ix = np.clip(ix, 0, [sx - 1, sy - 1])
+                pos = ss.index_to_position([ix[0], ix[1], rng.randint(0, sz)])
+                n_o = rng.randint(1, 4)
+                others = np.zeros((3, 3), dtype=np.int64)
+                for o in range(n_o):
+                    oi = np.clip(ix + rng.randint(-2, 3, size=2), 0, [sx - 1, sy - 1])
+                    others[o] = ss.index_to_position([oi[0], oi[1], rng.randint(0, sz)])
+                m = np.asarray(asp.get_action_mask(pos)[0], dtype=np.float64).copy()
+                cm_in.append(m.copy())
+                cm_out.append(np.asarray(asp.apply_collision_mask(pos, m, [others[o] for o in range(n_o)], ss), dtype=np.float64))
+                cp.append(pos)
+                co.append(others)
+                cn.append(n_o)
+            out[f"{k}_a{A}_col_pos"] = np.array(cp, dtype=np.int32)
+            out[f"{k}_a{A}_col_others"] = np.array(co, dtype=np.int32)
+            out[f"{k}_a{A}_col_n"] = np.array(cn, dtype=np.int32)
+            out[f"{k}_a{A}_col_in"] = np.array(cm_in, dtype=np.uint8)
+            out[f"{k}_a{A}_col_out"] = np.array(cm_out, dtype=np.uint8)
+    # one sensing + local fusion + global fusion round of the reference's Mapping on a 128 x 256 grid, three UAVs whose footprints
+    # clip at x = 0, at the far x and y borders, and at y = 0; correctness draws injected as in gen_bayes_measurement
+    p = make_params("small", environment__x_dim=50, environment__y_dim=100)
+    mp = _mapping(p, episode=3)
+    positions = np.array([[0, 35, 15], [50, 100, 10], [45, 90, 15], [25, 0, 5]])
+    real = torch.multinomial
+    sensed, corrs, m2c = [], [], {}
+    try:
+        for i, pos in enumerate(positions):
+            _, fc = Camera(p, AltitudeSensorModel(p), mp.grid_map).project_field_of_view(pos, mp.grid_map.resolution_x, mp.grid_map.resolution_y)
+            corr = (rng.random_sample((fc[3] - fc[2], fc[1] - fc[0])) > 0.2).astype(np.int64)
+            torch.multinomial = lambda w, n, replacement=True, _c=corr: torch.from_numpy(_c.flatten())
+            state, _, _, comm, _ = mp.update_grid_map(pos, mp.init_priors(), 0, "train")
+            sensed.append(state)
+            corrs.append(corr.astype(np.uint8).reshape(-1))
+            m2c[i] = {"map2communicate": comm}
+    finally:
+        torch.multinomial = real
+    out["seq_truth"] = np.packbits(np.asarray(mp.simulated_map, dtype=np.uint8), axis=None)
+    out["seq_positions"] = positions.astype(np.int32)
+    out["seq_corr"] = np.packbits(np.concatenate(corrs))
+    out["seq_corr_lens"] = np.array([len(c) for c in corrs], dtype=np.int32)
+    out["seq_sensed"] = np.array(sensed, dtype=np.float32)
+    out["seq_fused_local"] = np.array([mp.fuse_map(sensed[i].copy(), m2c, i, "local") for i in range(len(positions))], dtype=np.float32)
+    out["seq_global"] = np.asarray(mp.fuse_map(mp.init_priors(), m2c, None, "global"), dtype=np.float32)
+    save("rect_geometry", **out)
+
+
 # ------------------------------------------------------------------ 6: comm
 def gen_comm():
     rng = np.random.RandomState(5)
@@ -598,7 +694,7 @@ def gen_missions():
 
 
 GENERATORS = [gen_derived_and_footprints, gen_start_states, gen_truth, gen_terrain, gen_masks, gen_comm, gen_bayes_measurement,
-              gen_entropy_reward, gen_episodes, gen_episode_default_grid, gen_episode_prior_and_c4, gen_td_lambda, gen_coma_step, gen_ig_baseline, gen_missions]
+              gen_entropy_reward, gen_rect_geometry, gen_episodes, gen_episode_default_grid, gen_episode_prior_and_c4, gen_td_lambda, gen_coma_step, gen_ig_baseline, gen_missions]
 
 if __name__ == "__main__":
     check_schema()

@@ -19,9 +19,10 @@ for sub in ("oracle",):
         sys.path.insert(0, path)
 
 
-def philox_episode(params, episode, seed, truth=None):
+def philox_episode(params, episode, seed, truth=None, build_features=True):
     """One episode of the oracle under the production randomness (Philox flips / uniform valid actions / comm draws keyed by
-    (seed; episode, agent, step), mirrored from the device): (per-step log, final local maps [n, gx, gy], final global map)."""
+    (seed; episode, agent, step), mirrored from the device): (per-step log, final local maps [n, gx, gy], final global map).
+    ``build_features=False``: no network inputs (the networks are wired to an 11 x 11 lattice; other lattices run env-only)."""
     import ipp_oracle as O
     d = O.Derived(params)
     holder = {}
@@ -35,7 +36,7 @@ def philox_episode(params, episode, seed, truth=None):
         return O.uniform_valid_action(O.philox_action_word(seed, episode, i, t), mask)
 
     ep = O.OracleEpisode(params, episode, correctness, choose, comm_draw=lambda i, j, t: O.philox_comm_draw(seed, episode, i, j, t),
-                         build_features=True, exact=True, truth=truth)
+                         build_features=build_features, exact=True, truth=truth)
     holder["ep"] = ep
     log = ep.run()
     return log, np.array([a["local_map"] for a in ep.agents]), np.array(ep.global_map)
@@ -45,12 +46,12 @@ def _job(args):
     return philox_episode(*args)
 
 
-def philox_episodes(params, episodes, seed, truths=None, min_parallel_cells=1 << 19):
+def philox_episodes(params, episodes, seed, truths=None, min_parallel_cells=1 << 19, build_features=True):
     """[philox_episode(...)] for every episode of a batch; in worker processes when the grid is large enough to pay for them."""
     truths = [None] * len(episodes) if truths is None else list(truths)
     # (params: one dict for the batch, or one per episode -- mixed team sizes: env e is a run with its own n_agents)
     per_env = list(params) if isinstance(params, (list, tuple)) else [params] * len(episodes)
-    jobs = [(pr, int(ep), seed, tr) for pr, ep, tr in zip(per_env, episodes, truths)]
+    jobs = [(pr, int(ep), seed, tr, build_features) for pr, ep, tr in zip(per_env, episodes, truths)]
     import ipp_oracle as O
     d = O.Derived(max(per_env, key=lambda pr: pr["experiment"]["missions"]["n_agents"]))
     if len(jobs) < 2 or d.gx * d.gy * d.n_agents < min_parallel_cells:

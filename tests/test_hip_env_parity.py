@@ -130,7 +130,7 @@ def test_production_randomness_matches_oracle(name, over, n_envs):
 
 
 def check_philox_episodes(name, over, n_envs, seed=0x1234567ABC, first_episode=11, track_area=True, fused_step=False, terrain="split",
-                          team_sizes=None):
+                          team_sizes=None, map_layout="auto"):
     """The every-step comparison of a batch with the oracle under the production randomness; returns the number of class-weight
     threshold ties met (conftest).  (``seed`` / ``first_episode``: tools/stress_parity.py sweeps random configurations through it.)
     ``fused_step``: ``steps()`` alone, i.e. ONE plan launch (comm + plans + work list + K1) -> fusion -> K3, the exact launch
@@ -138,19 +138,22 @@ def check_philox_episodes(name, over, n_envs, seed=0x1234567ABC, first_episode=1
     compared after the step's sensing instead.  ``terrain="random_field"``: the device synthesises the field (bench.py's input);
     the generated truth is handed to the oracle, whose own field uses NumPy's legacy normal stream instead of Philox.
     ``team_sizes``: env e flies team_sizes[e] of the configured n_agents UAVs and is compared with an oracle run whose n_agents is
-    team_sizes[e] (the reference's team size is a per-run parameter)."""
+    team_sizes[e] (the reference's team size is a per-run parameter).  ``map_layout``: VecEnv's storage layout of the maps.  A lattice
+    other than 11 x 11 (a rectangular world) has no network inputs: the oracle builds none and the device steps with features=False."""
     from oracle_pool import philox_episodes
     from ippmarl.vec_env import POLICY_UNIFORM
     params = make_params(name, **over)
-    env = _env(params, n_envs, philox_seed=seed, track_area=track_area, terrain=terrain, team_sizes=team_sizes)
+    env = _env(params, n_envs, philox_seed=seed, track_area=track_area, terrain=terrain, team_sizes=team_sizes, map_layout=map_layout)
     eps = [first_episode + 7 * k for k in range(n_envs)]
     env.reset(eps)
     truths = None if terrain == "split" else list(env.truth_map.numpy().astype(np.float64))
     teams = [env.d.n_agents] * n_envs if team_sizes is None else [int(v) for v in team_sizes]
+    wired = env.d.space_x == env.d.space_y == 11   # (the lattice the networks are wired to)
     oracles = philox_episodes(params if team_sizes is None else
-                              [make_params(name, **dict(over, experiment__missions__n_agents=n_e)) for n_e in teams], eps, seed, truths)
+                              [make_params(name, **dict(over, experiment__missions__n_agents=n_e)) for n_e in teams], eps, seed, truths,
+                              build_features=wired)
     T = env.d.budget + 1
-    feats = track_area and not fused_step   # (the 493 x 493 default grid included: its feature bins are not whole cells wide)
+    feats = track_area and not fused_step and wired   # (the 493 x 493 default grid included: its feature bins are not whole cells wide)
     ties = 0
     for t in range(T):
         if fused_step:
@@ -298,12 +301,15 @@ def _field_checks(got, want, tag):
 def test_random_field_terrain_fft_path():
     """Grids that are not powers of two (default 493 x 493, odd: one zero amplitude row/column): device noise + rocFFT +
     threshold kernel against a float64 host evaluation of the same noise."""
+    check_fft_terrain(make_params("default"), np.array([3, 1000003, 17, 4]))
+
+
+def check_fft_terrain(params, eps):
+    """The checks of test_random_field_terrain_fft_path for the envs of ``eps`` on the grid of ``params`` (FFT path)."""
     from ippmarl import _ffi
     from ippmarl.terrain import amplitude_table
-    params = make_params("default")
-    E = 4
+    E = len(eps)
     env = _env(params, E, terrain="random_field")
-    eps = np.array([3, 1000003, 17, 4])
     env.reset(eps)
     assert not env_terrain(env).native
     got = env.truth_map.numpy()
@@ -331,12 +337,18 @@ def env_terrain(env):
 @pytest.mark.parametrize("name", ["small", "c2", "c5"])   # 128, 256, 1024 cells a side
 def test_random_field_terrain_native_path(name):
     """Power-of-two grids: spectrum drawn in the library + two-pass LDS inverse transform + threshold."""
+    check_native_terrain(make_params(name, experiment__missions__n_agents=2))
+
+
+def check_native_terrain(params, eps=(3, 1000003, 17)):
+    """The checks of test_random_field_terrain_native_path on the grid of ``params`` (each side 128, 256, 512 or 1024 cells): the
+    spectrum's bins against the host Philox + Box-Muller, its Hermitian columns, the inverse transform against NumPy, the packed truth
+    against reset()'s, and an episode's field independent of its batch.  ``eps``: three episodes."""
     from ippmarl import _ffi
     from ippmarl.terrain import amplitude_table
-    params = make_params(name, experiment__missions__n_agents=2)
-    E = 3
+    eps = np.array(eps)
+    E = len(eps)
     env = _env(params, E, terrain="random_field")
-    eps = np.array([3, 1000003, 17])
     env.reset(eps)
     assert env_terrain(env).native
     got = env.truth_map.numpy()

@@ -36,6 +36,36 @@ def test_derived_constants_match_reference(golden, name):
     assert d.tile_stride % 4 == 0 and d.tile_stride >= 2 * max(d.radius_y) + 3
 
 
+@pytest.mark.parametrize("key", ["small_50x100", "small_100x50", "small_50x200", "small_200x50", "c2_25x200", "c2_200x25", "c2_50x250",
+                                 "c4_25x50", "small_75x50", "small_45x50", "small_50x45", "c2_35x50"])
+def test_rect_derived_constants_match_reference(golden, key):
+    """The tables _ffi.make_config hands the device, on rectangular worlds (rect_geometry.npz): grid dims, resolution, lattice and the
+    footprint of every lattice point, whose x extent clips at grid_x and y extent at grid_y."""
+    fx = golden("rect_geometry")
+    name, dims = key.rsplit("_", 1)
+    x, y = (int(v) for v in dims.split("x"))
+    d = _derived(name, environment__x_dim=x, environment__y_dim=y)
+    assert [d.res_x, d.res_y] == list(fx[f"{key}_res"])
+    assert [d.grid_x, d.grid_y] == list(fx[f"{key}_dims"])
+    assert [d.space_x, d.space_y, d.space_z] == list(fx[f"{key}_space"])
+    full, clip = [], []
+    for ix in range(d.space_x):
+        for iy in range(d.space_y):
+            for iz in range(d.space_z):
+                f, c = d.footprint(d.index_to_position([ix, iy, iz]))
+                full.append(f), clip.append(c)
+    assert np.array_equal(np.array(full), fx[f"{key}_fp_full"])
+    assert np.array_equal(np.array(clip), fx[f"{key}_fp_clip"])
+    from ippmarl import _ffi
+    cfg = _ffi.make_config(d)
+    assert (cfg.grid_x, cfg.grid_y, cfg.space_x, cfg.space_y) == (d.grid_x, d.grid_y, d.space_x, d.space_y)
+    assert list(cfg.centre_x[:d.space_x]) == list(d.centre_x) and list(cfg.centre_y[:d.space_y]) == list(d.centre_y)
+    assert d.tile_stride % 4 == 0 and d.tile_stride >= 2 * max(d.radius_y) + 3
+    # the start states of the device's MT19937 mirror, which draws x on space_x and y on space_y
+    got = np.array([[_ffi.host_start_state(d.env_seed, e, a, d.spacing, d.space_x, d.space_y) for a in range(16)] for e in range(1, 33)])
+    assert np.array_equal(got, fx[f"{key}_starts"])
+
+
 def test_measurement_tables_match_reference_arithmetic(golden):
     d = _derived("c2")
     fx = golden("bayes_measurement")

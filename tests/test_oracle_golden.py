@@ -86,6 +86,74 @@ def test_action_masks_and_moves(golden, A):
         assert np.array_equal(got, m_out), (pos, others[:n], m_in, m_out, got)
 
 
+RECT_SETS = ["small_50x100", "small_100x50", "small_50x200", "small_200x50", "c2_25x200", "c2_200x25", "c2_50x250", "c4_25x50",
+             "small_75x50", "small_45x50", "small_50x45", "c2_35x50"]   # (oracle/make_golden.py: RECT_SETS)
+
+
+def rect_params(key, **over):
+    """make_params of a rect_geometry.npz key '<set>_<x_dim>x<y_dim>'."""
+    name, dims = key.rsplit("_", 1)
+    x, y = (int(v) for v in dims.split("x"))
+    return make_params(name, environment__x_dim=x, environment__y_dim=y, **over)
+
+
+def test_rect_fixture_holds_every_set(golden):
+    fx = golden("rect_geometry")
+    assert sorted(k[: -len("_dims")] for k in fx if k.endswith("_dims")) == sorted(RECT_SETS)
+
+
+@pytest.mark.parametrize("key", RECT_SETS)
+def test_rect_geometry(golden, key):
+    """Rectangular worlds (x_dim != y_dim): grid dims, resolution, lattice, start states, footprints (full / clipped / fixed) at every
+    lattice point, action masks at every lattice point (6 and 27 actions) and collision masks near all four borders, bit for bit."""
+    fx = golden("rect_geometry")
+    d = O.Derived(rect_params(key))
+    assert [d.res_x, d.res_y] == list(fx[f"{key}_res"])
+    assert [d.gx, d.gy] == list(fx[f"{key}_dims"]) and d.gx != d.gy
+    assert [d.space_x, d.space_y, d.space_z] == list(fx[f"{key}_space"])
+    got = np.array([[O.start_state(d, a, e) for a in range(16)] for e in range(1, 33)])
+    assert np.array_equal(got, fx[f"{key}_starts"])
+    full, clip, fixed = [], [], []
+    for pos in lattice(d):
+        f, c = O.project_field_of_view(d, pos)
+        full.append(f), clip.append(c), fixed.append(O.fixed_footprint_coordinates(f, c))
+    assert np.array_equal(np.array(full), fx[f"{key}_fp_full"])
+    assert np.array_equal(np.array(clip), fx[f"{key}_fp_clip"])
+    assert np.array_equal(np.array(fixed), fx[f"{key}_fp_fixed"])
+    for A in (6, 27):
+        dA = O.Derived(rect_params(key, experiment__constraints__num_actions=A))
+        got = np.array([O.action_mask(dA, pos) for pos in lattice(dA)])
+        assert np.array_equal(got, fx[f"{key}_a{A}_mask"]), A
+        for pos, others, n, m_in, m_out in zip(fx[f"{key}_a{A}_col_pos"], fx[f"{key}_a{A}_col_others"], fx[f"{key}_a{A}_col_n"],
+                                               fx[f"{key}_a{A}_col_in"], fx[f"{key}_a{A}_col_out"]):
+            got = O.apply_collision_mask(dA, pos, m_in.astype(np.float64), [others[k] for k in range(n)])
+            assert np.array_equal(got, m_out), (A, pos, others[:n], m_in, m_out, got)
+
+
+def test_rect_sensing_and_fusion(golden):
+    """One round of the reference's Mapping on a 128 x 256 grid (x_dim 50, y_dim 100): four UAVs whose footprints clip at x = 0, at
+    the far x and y borders and at y = 0 sense with recorded correctness draws, fuse each other's measurements locally and into a
+    global map -- the oracle's update_grid_map / fuse_map bit for bit."""
+    fx = golden("rect_geometry")
+    d = O.Derived(make_params("small", environment__x_dim=50, environment__y_dim=100))
+    assert (d.gx, d.gy) == (128, 256)
+    truth = np.unpackbits(fx["seq_truth"])[: d.gx * d.gy].reshape(d.gx, d.gy).astype(np.float64)
+    assert np.array_equal(truth, O.make_truth(d, 3))
+    bits = np.unpackbits(fx["seq_corr"])
+    offs = np.concatenate([[0], np.cumsum(fx["seq_corr_lens"])])
+    sensed, m2c = [], {}
+    for i, pos in enumerate(fx["seq_positions"]):
+        _, fc = O.project_field_of_view(d, pos)
+        corr = bits[offs[i]:offs[i + 1]].reshape(O.tile_shape(fc)).astype(np.int64)
+        state, _, _, comm, _ = O.update_grid_map(d, truth, pos, O.init_prior_map(d), corr)
+        sensed.append(state)
+        m2c[i] = {"map2communicate": comm}
+    assert np.array_equal(np.array(sensed, dtype=np.float32), fx["seq_sensed"])
+    fused = [O.fuse_map(d, sensed[i].copy(), m2c, i, "local") for i in range(len(sensed))]
+    assert np.array_equal(np.array(fused, dtype=np.float32), fx["seq_fused_local"])
+    assert np.array_equal(np.asarray(O.fuse_map(d, O.init_prior_map(d), m2c, None, "global"), dtype=np.float32), fx["seq_global"])
+
+
 def test_communication(golden):
     fx = golden("comm")
     for rg, fail, pos, draws, rec in zip(fx["range"], fx["failure"], fx["pos"], fx["draws"], fx["received"]):

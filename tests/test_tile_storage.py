@@ -190,3 +190,63 @@ def test_tiled_env_single_purpose_entry_points_and_metrics():
     torch.testing.assert_close(fb, fa, rtol=1e-12, atol=1e-9)
     torch.testing.assert_close(gb, ga, rtol=1e-6, atol=1e-9)
     torch.testing.assert_close(rb, ra, rtol=1e-6, atol=1e-6)
+
+
+# Configurations CASES above does not reach, each flown in tile storage against the oracle directly (not only against the row-major
+# env): every step's comm, masks, actions, positions, rects bit for bit, maps at 1e-5, rewards / S1 / S2 within check_philox_episodes'
+# bounds.  name, overrides, envs, team sizes (None: all fly), tracked form with network inputs
+ORACLE_CASES = {
+    "small_12uavs_range100": ("small", {"experiment__missions__n_agents": 12, "experiment__uav__communication_range": 100}, 1, None, False),
+    "small_16uavs_range100_27": ("small", {"experiment__missions__n_agents": 16, "experiment__uav__communication_range": 100,
+                                           "experiment__constraints__num_actions": 27}, 1, None, False),     # > 10 ops: generic fusion path
+    # (the cell size follows min_altitude (grid_maps.py:29-32): at a 15 m floor the small set's 15 pixels make a 42 x 42 grid, too narrow for
+    #  the tile form; 45 pixels make it 128 x 128 again, with the small set's footprints)
+    "small_2uavs_planar9": ("small", {"experiment__missions__n_agents": 2, "experiment__constraints__num_actions": 9,
+                                      "experiment__constraints__min_altitude": 15, "experiment__constraints__max_altitude": 15,
+                                      "sensor__pixel__number_x": 45, "sensor__pixel__number_y": 45}, 2, None, False),
+    "small_3uavs_4actions": ("small", {"experiment__missions__n_agents": 3, "experiment__constraints__num_actions": 4}, 3, None, False),
+    # 20 m is noise-free: cells hold +-inf log-odds until the next fusion clips them
+    "small_noise_free": ("small", {"experiment__constraints__min_altitude": 15, "experiment__constraints__max_altitude": 20,
+                                   "experiment__constraints__num_actions": 27, "experiment__uav__communication_range": 10,
+                                   "sensor__pixel__number_x": 45, "sensor__pixel__number_y": 45}, 2, None, False),
+    "136x136": ("small", {"sensor__pixel__number_x": 16, "sensor__pixel__number_y": 16}, 2, None, False),   # whole tiles, not a power of two
+    "264x264": ("small", {"sensor__pixel__number_x": 31, "sensor__pixel__number_y": 31}, 2, None, False),
+    "small_tracked_features": ("small", {}, 3, None, True),
+    "mixed_small": ("small", {"experiment__missions__n_agents": 6}, 6, [1, 2, 3, 6, 4, 5], False),
+    "mixed_small27": ("small", {"experiment__missions__n_agents": 5, "experiment__uav__failure_rate": 0.3, "experiment__uav__fix_range": False,
+                                "experiment__constraints__num_actions": 27}, 3, [5, 2, 4], False),
+    "c5_3uavs": ("c5", {"experiment__missions__n_agents": 3}, 1, None, False),   # 1024^2: line rounding on
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,fused_step", [(c, f) for c in ORACLE_CASES for f in ((False,) if ORACLE_CASES[c][4] else (False, True))])
+def test_tiled_env_matches_oracle(case, fused_step):
+    """A tile-stored env against the oracle, every step (the tracked form builds its network inputs between two plan launches, so it
+    runs in that form only, not in the one-launch step)."""
+    from test_hip_env_parity import check_philox_episodes
+    name, over, n_envs, teams, features = ORACLE_CASES[case]
+    check_philox_episodes(name, over, n_envs, seed=0x711E5, first_episode=9, track_area=features, fused_step=fused_step, team_sizes=teams,
+                          map_layout="tiles")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,n_envs", [("c2", 3), ("small", 4)])
+def test_tiled_benched_combination_matches_oracle(name, n_envs):
+    """test_benched_combination_matches_oracle's arguments (device-synthesised terrain, no area sums, one plan launch a step) in tile storage."""
+    from test_hip_env_parity import check_philox_episodes
+    check_philox_episodes(name, {}, n_envs, seed=3, first_episode=1, track_area=False, fused_step=True, terrain="random_field", map_layout="tiles")
+
+
+@pytest.mark.gpu
+def test_shifted_prior_refuses_tiles(monkeypatch):
+    """prior != 0.5 runs the explicit slow path (no tile form of the fusion): "tiles" is refused, "auto" keeps rows whatever the batch."""
+    from ippmarl import _ffi
+    from ippmarl.vec_env import VecEnv
+    monkeypatch.delenv("IPPM_MAP_TILED", raising=False)
+    params = make_params("c4", mapping__prior=0.3)
+    with pytest.raises(_ffi.IppmError):
+        VecEnv(params, 1, map_layout="tiles", track_area=False)
+    env = VecEnv(params, 1, map_layout="auto", track_area=False, layout_envs=1024)
+    assert not env.tiled and not env._tile_form
+    assert VecEnv(make_params("c4"), 1, map_layout="auto", track_area=False, layout_envs=1024).tiled   # (the same batch at prior 0.5)
