@@ -149,7 +149,8 @@ int ippm_read_counters(ippm_ctx* ctx, ippm_counters* out, int reset, void* strea
 #define IPPM_T_RESET 5        /* reset: scalars, truth split, prior fills */
 #define IPPM_T_TERRAIN 6      /* random-field synthesis passes */
 #define IPPM_T_RESET_MAPS 7   /* ippm_reset_maps: box-limited prior fill + start-position sensing */
-#define IPPM_TIMED_CLASSES 8
+#define IPPM_T_AGENT_REWARD 8 /* ippm_agent_rewards: k_agent_rewards */
+#define IPPM_TIMED_CLASSES 9
 int ippm_kernel_timing(ippm_ctx* ctx, int32_t enable);
 int ippm_read_kernel_times(ippm_ctx* ctx, int32_t cls, int32_t reset, int64_t* launches, double* total_us, double* min_us,
                            char* name, int32_t name_len, void* stream);
@@ -312,6 +313,25 @@ int ippm_fuse_step(ippm_ctx* ctx, float* local, float* global, const uint8_t* co
 int ippm_work_words(ippm_ctx* ctx, int32_t n_envs, int64_t* words); /* length of `work` in int32 words for n_envs envs */
 int ippm_tile_form(ippm_ctx* ctx, int32_t* yes); /* 1: this configuration has the tile form (IPPM_STEP_TILES) */
 int ippm_reward_finalize(ippm_ctx* ctx, double* sums, float* reward, int32_t n_envs, void* stream);
+
+/* ---- DeepQ per-agent information-gain rewards (coma_wrapper.py:113-133 with mission type "DeepQ"; utils/reward.py:11-82,
+ * utils/state.py:53-121, mappings.py:109-124).  For every agent i of env e: the reward of fusing ONLY agent i's fresh measurement
+ * m_i into the global map K of this step, get_global_reward(K, K (+) m_i):
+ *   S1_i = sum over cells of w(K (+) m_i) (H(K) - H(K (+) m_i)),  S2_i = sum of w(K (+) m_i) H(K) = T + sum (w(K (+) m_i) - w(K)) H(K)
+ * with T = sums[e][2], the running weighted entropy of K, and agent_reward[e,i] = (22 S1_i/S2_i - 0.5, 10 S1_i/(gx*gy) - 0.17).
+ * K (+) m_i clips every cell of K and adds the measurement's log-odds minus logit(prior): with prior 0.5 only agent i's footprint
+ * differs from K, with any other prior every cell shifts (the kernel then walks the whole grid).
+ *   global   float [E,gx,gy] in the context's map layout: K, read only;
+ *   code     the measurement codes K3 wrote for the new positions;
+ *   rect     int32 [E,N,IPPM_SENSE_REC_WORDS]: the sense records of the new footprints (ippm_plan_step's rect_next: footprint
+ *            words 0-3, float bits of the two measurement log-odds minus logit(prior) in words 4-5);
+ *   sums     double [E,8] after the step's reward was completed (reads [e][2] = T(K));
+ *   agent_sums   double [E,N,2] = (S1_i, S2_i), optional (NULL);  agent_reward float [E,N,2] = (relative, absolute).
+ * Agents that do not fly (ippm_set_team_sizes) get 0 in both outputs.  Writes nothing else.
+ * Call after ippm_sense_step(sums, reward) of the batched step (or, one env at a time, after the last agent's sensing and the
+ * reward of ippm_fuse_global_reward) and before the next fusion writes K or the codes. */
+int ippm_agent_rewards(ippm_ctx* ctx, const float* global, const uint8_t* code, const int32_t* rect, const double* sums,
+                       double* agent_sums, float* agent_reward, int32_t n_envs, void* stream);
 
 /* Full-grid weighted entropy sum(w(p) H(p)) per map (utils/state.py:53-121, "reward" mode); n_maps maps of
  * gx*gy floats; out float64 [n_maps].  truth != NULL: weights from ground truth ("eval" mode), map m uses

@@ -70,13 +70,7 @@ struct WaveAcc {
   unsigned cells, opcells;
 };
 
-// Shannon entropy of sigmoid(clamp(l)) in float64 (SHIFT path: the float32 form's 1e-7 absolute error per cell, summed over
-// a whole grid of barely changed cells, would show at 1e-4 in the returns)
-__device__ __forceinline__ double entropy_l_f64(float l, float lc) {
-  const double a = fmin(fabs((double)l), (double)lc);
-  const double e = exp(-a), d = 1.0 + e;
-  return log2(d) + a * 1.4426950408889634 * (e / d);
-}
+// (entropy_l_f64, the SHIFT path's float64 entropy: ippm_internal.h, shared with k_agent_rewards)
 
 #ifndef IPPM_FUSE_LOAD_AUX   // cache policy of the map accesses (bit 1 = non-temporal on gfx950)
 #define IPPM_FUSE_LOAD_AUX 0

@@ -209,6 +209,13 @@ __device__ __forceinline__ float ippm_entropy_l(float l, float lc) {
   const float d = 1.0f + e;
   return __log2f(d) + (a * 1.44269504f) * (e * __builtin_amdgcn_rcpf(d));
 }
+// Shannon entropy of sigmoid(clamp(l)) in float64 (SHIFT path of the fusion, mapping.prior != 0.5: the float32 form's 1e-7 absolute
+// error per cell, summed over a whole grid of barely changed cells, would show at 1e-4 in the returns)
+__device__ __forceinline__ double entropy_l_f64(float l, float lc) {
+  const double a = fmin(fabs((double)l), (double)lc);
+  const double e = exp(-a), d = 1.0 + e;
+  return log2(d) + a * 1.4426950408889634 * (e / d);
+}
 // entropy of a probability (used on the 11x11 resized planes)
 __device__ __forceinline__ float ippm_entropy(float p, float lo, float hi) {
   p = ippm_clipf(p, lo, hi);
@@ -303,6 +310,14 @@ __device__ __forceinline__ void ippm_footprint_rect(const ippm_config* c, int px
 }
 
 
+// (relative, absolute) reward from S1 = sum w(a) (H(b) - H(a)) and S2 = sum w(a) H(b) (utils/reward.py:25-40): the COMA team reward
+// (ippm_reward_finalize_env) and the DeepQ per-agent rewards (k_agent_rewards) go through this one expression
+__device__ __forceinline__ void ippm_reward_pair(const ippm_config* __restrict__ c, double s1, double s2, float* __restrict__ out) {
+  const double cells = (double)c->grid_x * (double)c->grid_y;
+  out[0] = (float)(22.0 * (s1 / s2) - 0.5);        // utils/reward.py:38-40
+  out[1] = (float)(10.0 * (s1 / cells) - 0.17);    // utils/reward.py:37
+}
+
 // reward of one env from the sums K5 accumulated (utils/reward.py:25-40,74-82); rolls the running weighted entropy T forward
 __device__ __forceinline__ void ippm_reward_finalize_env(const ippm_config* __restrict__ c, double* __restrict__ sums,
                                                          float* __restrict__ reward, int e) {
@@ -313,9 +328,7 @@ __device__ __forceinline__ void ippm_reward_finalize_env(const ippm_config* __re
   s[SUM_S2] = s2;
   s[SUM_T] += s[SUM_ACCT];
   s[SUM_ACC1] = 0; s[SUM_ACCD] = 0; s[SUM_ACCT] = 0;
-  const double cells = (double)c->grid_x * (double)c->grid_y;
-  reward[e * 2] = (float)(22.0 * (s1 / s2) - 0.5);        // utils/reward.py:38-40
-  reward[e * 2 + 1] = (float)(10.0 * (s1 / cells) - 0.17);  // utils/reward.py:37
+  ippm_reward_pair(c, s1, s2, reward + e * 2);
 }
 
 // ---- legacy NumPy MT19937: first outputs of RandomState(seed) and the masked-rejection bounded draw ----

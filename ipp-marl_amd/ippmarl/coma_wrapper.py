@@ -84,8 +84,16 @@ class COMAWrapper:
             get_critic_input(t, global_information, None, batch_memory, agent_id, simulated_map, params)
         next_global_map = engine.get_global()
         mapping._global_token = next_global_map
-        relative_reward, absolute_reward = (float(v) for v in env.reward[0].cpu())
         done = t == self.budget
-        for agent_id in range(self.n_agents):
-            batch_memory.insert(-1, agent_id, reward=relative_reward, done=done)
+        if self.mission_type == "DeepQ":
+            # coma_wrapper.py:113-133: agent i's transition gets the reward of fusing only ITS fresh measurement into the step's
+            # global map; the COMA team reward is skipped (:149-171) and the LAST agent's pair is returned
+            per_agent = env.agent_rewards_from_rect()[0].cpu().numpy()
+            for agent_id in range(self.n_agents):
+                batch_memory.insert(-1, agent_id, reward=float(per_agent[agent_id, 0]), done=done)
+            relative_reward, absolute_reward = float(per_agent[-1, 0]), float(per_agent[-1, 1])
+        else:
+            relative_reward, absolute_reward = (float(v) for v in env.reward[0].cpu())
+            for agent_id in range(self.n_agents):
+                batch_memory.insert(-1, agent_id, reward=relative_reward, done=done)
         return (batch_memory, relative_reward, absolute_reward, done, next_positions, eps, actions, altitudes, next_global_map)

@@ -26,6 +26,12 @@ class COMATrainer:
         self.params = params
         # team_sizes: mixed team sizes in one batch (VecEnv): the transitions of agents that do not fly never enter a minibatch
         self.env = VecEnv(params, n_envs, device=device, philox_seed=philox_seed, terrain=terrain, team_sizes=team_sizes)
+        # mission type DeepQ (coma_wrapper.py:113-171): every agent's transition carries ITS information gain (VecEnv.agent_reward, on
+        # for DeepQ), each (env, agent) TD chain is built from its own rewards, and the return is the last flying agent's, as the
+        # reference's EpisodeGenerator sums it; team_return keeps the COMA team reward beside it
+        self.deepq = params["experiment"]["missions"].get("type") == "DeepQ"
+        if self.deepq and not self.env.agent_rewards:
+            raise _ffi.IppmError("COMATrainer: mission type DeepQ needs the per-agent rewards of the env")
         # Large batches: where the allocator put the maps decides ~10 % of the rollout's map kernels (VecEnv.tune_placement).  The
         # search is OPT-IN (placement_draws > 1; bench.py passes its own --placement-draws): it steps the env for ~10 ms a draw and
         # holds candidate arenas within half of the free memory while it runs, which a caller should ask for, not find out about.
@@ -65,7 +71,11 @@ class COMATrainer:
         self.buf_state = torch.empty(W, T, E, N, 11, 11, 12, device=dev)
         self.buf_action = torch.empty(W, T, E, N, dtype=torch.int32, device=dev)
         self.buf_mask = torch.empty(W, T, E, N, self.A, dtype=torch.uint8, device=dev)
-        self.buf_reward = torch.empty(W, T, E, device=dev)
+        # rewards: one per env (COMA: the team reward, broadcast to its agents' chains) or one per (env, agent) (DeepQ)
+        self.buf_reward = torch.empty(W, T, E, N, device=dev) if self.deepq else torch.empty(W, T, E, device=dev)
+        # index of the last agent that flies in each env: whose reward a DeepQ episode's return sums (coma_wrapper.py:113-171)
+        last = (self.env.n_active.long() - 1) if self.env.n_active is not None else torch.full((E,), N - 1, dtype=torch.long, device=dev)
+        self._last_agent = last.view(E, 1, 1).expand(E, 1, 2).contiguous()
         self.wave = 0          # rollout waves done so far (defines the episode numbers)
         self.filled = 0        # waves currently in the buffer
         self.train_step = 0
@@ -73,6 +83,7 @@ class COMATrainer:
         self.eps_dev = torch.full((), float(self.eps), dtype=torch.float32, device=dev)   # epsilon as the graphs read it
         self.ret = torch.zeros(E, device=dev)
         self.abs_ret = torch.zeros(E, device=dev)
+        self.team_ret = torch.zeros(E, device=dev)   # the COMA team reward summed (= ret unless DeepQ)
         self.keep_rollout_log = False
         self.last_rollout = None
         self.last_diagnostics = None
@@ -88,6 +99,7 @@ class COMATrainer:
         env.reset(eps_ids)
         w = self.filled
         ret, abs_ret = self.ret.zero_(), self.abs_ret.zero_()
+        self.team_ret.zero_()
         policy = POLICY_ARGMAX if mode == "eval" else POLICY_SAMPLE
         step_rewards, step_actions, step_altitudes = [], [], []
         replay = self._step_graphs is not None and mode == "train" and w == 0 and not self.keep_rollout_log
@@ -110,8 +122,8 @@ class COMATrainer:
         self.wave += 1
         if mode == "train":
             self.filled += 1
-        return {"episode_return": float(ret.mean()), "absolute_return": float(abs_ret.mean()), "eps": self.eps,
-                "faults": int(env.fault.ne(0).sum())}
+        return {"episode_return": float(ret.mean()), "absolute_return": float(abs_ret.mean()),
+                "team_return": float(self.team_ret.mean()), "eps": self.eps, "faults": int(env.fault.ne(0).sum())}
 
     def _rollout_step(self, t: int, w: int, policy: int, store: bool, eps):
         """One lock-step env step of all E envs: observations -> actor -> move + sense (+ the transition into the buffer)."""
@@ -120,15 +132,24 @@ class COMATrainer:
         with torch.no_grad():
             probs, _ = self.actor(obs.view(self.E * self.N, 11, 11, 7), eps)
         reward, done, state = env.steps(t, policy=policy, probs=probs.view(self.E, self.N, self.A))
+        team = reward
+        if self.deepq:
+            reward = self.last_agent_reward()
         if store:
             self.buf_obs[w, t].copy_(obs)
             self.buf_state[w, t].copy_(state)
             self.buf_action[w, t].copy_(env.action)
             self.buf_mask[w, t].copy_(env.mask)
-            self.buf_reward[w, t].copy_(reward[:, 0])
+            self.buf_reward[w, t].copy_(env.agent_reward[..., 0] if self.deepq else reward[:, 0])
         self.ret += reward[:, 0]
         self.abs_ret += reward[:, 1]
+        self.team_ret += team[:, 0]
         return reward
+
+    def last_agent_reward(self) -> torch.Tensor:
+        """[E, 2] DeepQ (relative, absolute) reward of the last agent that flies in each env: what the reference's wrapper returns
+        and EpisodeGenerator sums into the episode's return (coma_wrapper.py:113-171)."""
+        return self.env.agent_reward.gather(1, self._last_agent).squeeze(1)
 
     def capture_graphs(self):
         """Records the launch-bound round into hipGraphs: one graph per rollout step t of a training wave (the step number is an
@@ -144,7 +165,8 @@ class COMATrainer:
         env.profile = False
         torch.cuda.synchronize(self.device)
         saved = {k: getattr(env, k).clone() for k in ("local", "glob", "ws", "sums", "pos", "pos_pre", "comm", "mask", "action", "fault",
-                                                       "reward", "area", "rect", "rect_next", "code", "work")}
+                                                       "reward", "area", "rect", "rect_next", "code", "work")
+                 + (("agent_reward", "agent_sums") if env.agent_rewards else ())}
         stream = torch.cuda.Stream(device=self.device)
         graphs = []
         for t in range(self.T):
@@ -184,7 +206,9 @@ class COMATrainer:
                 q_sel[lo:lo + chunk] = q.view(-1, self.A).gather(1, actions[lo:lo + chunk].long().view(-1, 1)).squeeze(1)
         # chains: [E*N, W*T]
         q_sel = q_sel.view(W, T, E, N).permute(2, 3, 0, 1).reshape(E * N, W * T).contiguous()
-        rew = self.buf_reward[:W].unsqueeze(-1).expand(W, T, E, N).permute(2, 3, 0, 1).reshape(E * N, W * T).contiguous()
+        # (COMA: the env's team reward on each of its agents' chains; DeepQ: each agent's own)
+        per_agent = self.buf_reward[:W] if self.deepq else self.buf_reward[:W].unsqueeze(-1).expand(W, T, E, N)
+        rew = per_agent.permute(2, 3, 0, 1).reshape(E * N, W * T).contiguous()
         done = torch.zeros(W, T, dtype=torch.uint8, device=self.device)
         done[:, T - 1] = 1
         done = done.view(1, W * T).expand(E * N, W * T).contiguous()
@@ -353,7 +377,7 @@ class COMATrainer:
         the per-step curves of target entropy and F1.  Index 0 = the prior map, index t+1 = the map holding every
         measurement up to and including the sensing of step t (coma_test.py:84-97,150-196).  ``counts_log`` (a list) receives, per
         scored map, the pair of int64 [E,3] count tensors of f1_counts at log-odds thresholds +1e-5 and -1e-5."""
-        returns, ent_curves, f1_curves = [], [], []
+        returns, team_returns, ent_curves, f1_curves = [], [], [], []
 
         def log_counts(glob=None):
             if counts_log is not None:
@@ -367,12 +391,14 @@ class COMATrainer:
             log_counts()
             ents, f1s = [e0.mean().item()], [f0.mean().item()]
             ret = torch.zeros(self.E, device=self.device)
+            team_ret = torch.zeros(self.E, device=self.device)
             for t in range(self.T):
                 obs = env.build_observations(t)
                 with torch.no_grad():
                     probs, _ = self.actor(obs.view(self.E * self.N, 11, 11, 7), self.eps)
                 reward, _, _ = env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(self.E, self.N, self.A))
-                ret += reward[:, 0]
+                team_ret += reward[:, 0]
+                ret += (self.last_agent_reward() if self.deepq else reward)[:, 0]
                 pending = self.global_map_with_pending()
                 e, f = self.map_metrics(pending)
                 log_counts(pending)
@@ -380,10 +406,12 @@ class COMATrainer:
                 f1s.append(f.mean().item())
             self.wave += 1
             returns.append(float(ret.mean()))
+            team_returns.append(float(team_ret.mean()))
             ent_curves.append(ents)
             f1_curves.append(f1s)
         mean = lambda rows: [sum(c) / len(c) for c in zip(*rows)]  # noqa: E731
-        return {"episode_return": sum(returns) / len(returns), "target_entropy": mean(ent_curves), "f1": mean(f1_curves)}
+        return {"episode_return": sum(returns) / len(returns), "team_return": sum(team_returns) / len(team_returns),
+                "target_entropy": mean(ent_curves), "f1": mean(f1_curves)}
 
     def returns_on(self, episodes, policy: str = "actor") -> Dict[str, float]:
         """Mean return of ``policy`` over the FIXED ``episodes`` (E ids: same truth, start cells and sensor noise whoever flies them --

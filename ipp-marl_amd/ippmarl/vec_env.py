@@ -97,7 +97,8 @@ def placement_stop_reason(scores, jumps: int = 0) -> Optional[str]:
 
 class VecEnv:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, terrain: str = "split",
-                 track_area: bool = True, team_sizes=None, map_layout: str = "auto", layout_envs: Optional[int] = None):
+                 track_area: bool = True, team_sizes=None, map_layout: str = "auto", layout_envs: Optional[int] = None,
+                 agent_rewards: Optional[bool] = None):
         if not torch.cuda.is_available():
             raise _ffi.IppmError("VecEnv needs an AMD GPU (HIP): there is no CPU path for the env step")
         self.params = params
@@ -183,6 +184,15 @@ class VecEnv:
         self.ws = z(E, N + 1, _ffi.WS_WORDS, dtype=torch.int32)
         self.sums = z(E, 8, dtype=torch.float64)
         self.reward = z(E, 2, dtype=torch.float32)
+        # DeepQ per-agent rewards (ippm_agent_rewards; coma_wrapper.py:113-133): agent i's information gain of fusing only its own fresh
+        # measurement into this step's global map.  None: on exactly when the mission type is DeepQ; True: in any mode (a diagnostic of
+        # COMA's credit assignment).  `reward` keeps its COMA (team) meaning either way; off: nothing is allocated or launched.
+        if agent_rewards is None:
+            agent_rewards = params["experiment"]["missions"].get("type") == "DeepQ"
+        self.agent_rewards = bool(agent_rewards)
+        self.agent_reward = z(E, N, 2, dtype=torch.float32) if self.agent_rewards else None   # (relative, absolute) per agent
+        self.agent_sums = z(E, N, 2, dtype=torch.float64) if self.agent_rewards else None     # (S1_i, S2_i)
+        self._lm_table = self._records = None   # (agent_rewards_from_rect's sense records, built on first use)
         self.split_pct = z(E, 2, dtype=torch.int32)
         # work list of a step's fusion: the plan kernel lists the non-empty (map, run of rows) items, the fusion kernel's
         # resident wavefronts stride over them
@@ -499,8 +509,34 @@ class VecEnv:
                           self._p(self.action), self._p(self.obs), self._p(self.state), self.E, self.stream)
             state = self.state
         self._sense(stage=t + 1, flips=flips, close_step=True)
+        if self.agent_rewards:
+            self._agent_rewards(self.rect_next)
         self.t = t + 1
         return self.reward, t == d.budget, state
+
+    def _agent_rewards(self, records: torch.Tensor):
+        """DeepQ per-agent rewards of the step just closed (after K3 and the step's reward, before the next fusion) from the sense
+        records of the new footprints -> agent_reward [E,N,2], agent_sums [E,N,2]."""
+        self.ctx.call("ippm_agent_rewards", self._p(self.glob), self._p(self.code), self._p(records), self._p(self.sums),
+                      self._p(self.agent_sums), self._p(self.agent_reward), self.E, self.stream)
+
+    def agent_rewards_from_rect(self) -> torch.Tensor:
+        """DeepQ per-agent rewards for callers that sense agent by agent (the drop-in engine) and have no plan launch to write sense
+        records: the records are built from the footprints in `rect` and the altitudes in `pos` (what ippm_plan_step writes into
+        rect_next for K3), then ippm_agent_rewards runs.  Call after the last agent's sensing of the step, before the next fusion.
+        -> agent_reward [E,N,2]."""
+        if not self.agent_rewards:
+            raise _ffi.IppmError("agent_rewards_from_rect: this env was built with agent_rewards=False")
+        d = self.d
+        if self._lm_table is None:   # measurement log-odds - logit(prior) per altitude level, float32 as the plan kernel forms them
+            lm = np.asarray(d.logit_meas, dtype=np.float32) - np.float32(d.logit_prior)
+            self._lm_table = torch.from_numpy(lm).to(self.device)
+            self._records = torch.zeros(self.E, d.n_agents, _ffi.SENSE_REC_WORDS, dtype=torch.int32, device=self.device)
+        k = torch.div(self.pos[..., 2] - d.min_altitude, d.spacing, rounding_mode="floor").clamp(0, d.space_z - 1).long()
+        self._records[..., :4] = self.rect
+        self._records[..., 4:6] = self._lm_table[k].view(torch.int32)
+        self._agent_rewards(self._records)
+        return self.agent_reward
 
     # ---- greedy information-gain policy (IG_baseline.py:127-148, 222-325) for the whole batch ---------------------
     def ig_actions(self, communication: bool = True) -> torch.Tensor:
@@ -548,6 +584,8 @@ class VecEnv:
         """One random-policy env step: graph replay (comm, plans, K1, K4, K5) + K3."""
         self._graphs[t].replay()
         self._sense(stage=t + 1, close_step=True)
+        if self.agent_rewards:
+            self._agent_rewards(self.rect_next)
         self.t = t + 1
         return self.reward, t == self.d.budget
 
@@ -709,7 +747,7 @@ class SplitVecEnv:
     through one actor batch and use ``VecEnv`` directly."""
 
     def __init__(self, params: Dict, n_envs: int, parts: int = 2, device: str = "cuda:0", philox_seed: int = 3, terrain: str = "split",
-                 track_area: bool = False, team_sizes=None, map_layout: str = "auto"):
+                 track_area: bool = False, team_sizes=None, map_layout: str = "auto", agent_rewards: Optional[bool] = None):
         if parts < 1 or n_envs < parts:
             raise ValueError("SplitVecEnv: 1 <= parts <= n_envs")
         self.device = torch.device(device)
@@ -725,10 +763,12 @@ class SplitVecEnv:
         for k, (n, off) in enumerate(zip(self.sizes, self.offsets)):
             with torch.cuda.stream(self.streams[k]):
                 self.parts.append(VecEnv(params, n, device=device, philox_seed=philox_seed, terrain=terrain, track_area=track_area,
-                                         team_sizes=None if ts is None else ts[off:off + n], map_layout=map_layout, layout_envs=int(n_envs)))
+                                         team_sizes=None if ts is None else ts[off:off + n], map_layout=map_layout, layout_envs=int(n_envs),
+                                         agent_rewards=agent_rewards))
         self.E = int(n_envs)
         self.d = self.parts[0].d
         self.tiled = self.parts[0].tiled
+        self.agent_rewards = self.parts[0].agent_rewards
         self.params = params
 
     # -- stream plumbing ------------------------------------------------------------------------------
@@ -895,3 +935,5 @@ class SplitVecEnv:
     mask = property(lambda self: self._cat("mask"))
     fault = property(lambda self: self._cat("fault"))
     sums = property(lambda self: self._cat("sums"))
+    agent_reward = property(lambda self: self._cat("agent_reward") if self.agent_rewards else None)
+    agent_sums = property(lambda self: self._cat("agent_sums") if self.agent_rewards else None)
