@@ -64,7 +64,6 @@ extern "C" int ippm_host_truth_params(int64_t episode, int32_t* out2) {
 // footprint row in 4-cell groups and the maps' storage layout; called at ippm_ctx_create and whenever the layout changes (ippm_set_map_layout).
 static void ippm_resolve_k3_shape(ippm_ctx* ctx) {
   const ippm_config& c = ctx->cfg;
-  auto knob = [](const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; };
   int wmax = 1;
   for (int k = 0; k < c.space_z; ++k) wmax = std::max(wmax, (2 * c.radius_y[k] + 3) / 4 + 1);
   const bool narrow = wmax <= 64;
@@ -73,13 +72,14 @@ static void ippm_resolve_k3_shape(ippm_ctx* ctx) {
   // workgroups with two loads in flight; long rows (a load instruction no longer spans a row segment): fewer, with three.
   // ... and the order of its workgroups: with rows of up to 32 groups (256^2) consecutive workgroups take the agents of an env (a map's parts n workgroups
   // apart): 33.94 - 34.04 -> 33.54 - 33.70 us in four alternating processes; 512^2 63.0 -> 63.5, 1024^2 91.3 -> 96.6: the parts of a footprint first there.
+  // (every shape chosen here has its instantiation of k_sense_tiles in ippm_sense_step: rows (2,2,1) (2,2,0) (4,3,0), tiles (1,3,0) (2,2,0) (4,3,0))
   int wpg = narrow ? 2 : 4, chn = narrow ? 2 : 3, go = wmax <= 32 ? 1 : 0;
   // Tile storage on 256^2-class grids: whole lines cost the memory side less, and a third load in flight per lane pays (profiles/r06/tile_storage_ab.txt:
   // 2048 envs x 4 UAVs (2,2,1) 66.2 us, (1,3,0) 57.7, (2,3,0) 57.7, (2,4,0) 60.8; 1024 envs x 8 UAVs 66.2 / 58.1 / 61.6 / 61.3); at 512^2 (2,2,0) stays (239 us; (1,3,0) 245).
   if (ctx->tl && wmax <= 32) { wpg = 1; chn = 3; go = 0; }
-  ctx->k3_wpg = knob("IPPM_K3_WPG", wpg);
-  ctx->k3_chn = knob("IPPM_K3_CHN", chn);
-  ctx->k3_go = knob("IPPM_K3_GO", go);
+  ctx->k3_wpg = wpg;
+  ctx->k3_chn = chn;
+  ctx->k3_go = go;
 }
 
 extern "C" int ippm_ctx_create(const ippm_config* cfg, ippm_ctx** out) {
@@ -111,33 +111,11 @@ extern "C" int ippm_ctx_create(const ippm_config* cfg, ippm_ctx** out) {
   // tools/probe/unaligned_probe.cpp), the last group of a row hangs over into the next row and is stored cell by cell, and a
   // group's four Philox words / truth bits straddle two counter values / two bytes (the reference's default 493 x 493).
   ctx->vec = (c.grid_y >= 4 * IPPM_FEAT) ? 4 : 1;
-  // tuning knobs are read once, here: the size of the caller's work buffer, the plan kernel's item layout and the fusion launch
-  // all follow from them, and a value that changed between two calls would make them disagree
+  // the environment knobs are read once, here: the size of the caller's work buffer, the plan kernel's item layout and the fusion launch
+  // all follow from the context's settings, and a value that changed between two calls would make them disagree
   auto knob = [](const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; };
-  ctx->knob_wave_rows = knob("IPPM_FUSE_WAVE_ROWS", 0);
-  ctx->knob_persist = knob("IPPM_FUSE_PERSIST", 0);
-  ctx->knob_nowork = knob("IPPM_FUSE_NOWORK", 0);
-  ctx->knob_split = knob("IPPM_FUSE_SPLIT", 0);
-  ctx->knob_tile_waves = knob("IPPM_TILE_WAVES", 0);
   ctx->knob_tile_rotate = knob("IPPM_TILE_ROTATE", -1);   // -1: by the launch (fuse_tiles.hip); 0: off; k: groups of 2^(k-1) wavefronts
-  ctx->knob_plan_builders = knob("IPPM_PLAN_BUILDERS", 0);
-  // Workgroup shape of the env-only step's K3 (wavefronts per workgroup x loads in flight per lane), by the width of the widest
-  // footprint row in 4-cell groups.  Measured on one allocation per grid, alternating episodes (tools/ab_knobs.py,
-  // profiles/r05/k3_workgroup_shapes.txt): 256^2 (W = 23): (4,3) 35.2 us, (2,2) 34.4; 512^2 (W = 46): (4,3) 67.6, (2,2) 64.2, (1,3)
-  // 69.9; 1024^2 (W = 91): (4,3) 94.5, (2,3) 93.8, (2,2) 100.4, (4,4) 162.7.  Short rows: many small workgroups with two loads in
-  // flight; long rows (a load instruction no longer spans a row segment): fewer, with three.
-  ippm_resolve_k3_shape(ctx);
-  // the tile fusion's column intervals rounded outwards to whole 128-byte lines (step_small.hip, tile_build_map): 1 on, 0 off, default: on
-  // for rows of at least 512 cells.  Measured (round 6, profiles/r06/tile_round_ab.txt): 512^2 x 8 UAVs fusion 1045 -> 1024 us and the K3
-  // behind it 286 -> 275; 256^2 x 4 UAVs fusion 74.7 -> 83-87 us (a 90-cell row grows from 3.7 to 4.7 lines' worth of lane-loads there)
-  ctx->knob_tile_round = knob("IPPM_TILE_ROUND", -1);
-  if (ctx->knob_tile_round < 0) ctx->knob_tile_round = ctx->cfg.grid_y >= 512 ? 1 : 0;
-  ctx->knob_k3_round = knob("IPPM_K3_ROUND", -1);        // the same for K3's row segments (env_step.hip)
-  if (ctx->knob_k3_round < 0) ctx->knob_k3_round = ctx->cfg.grid_y >= 512 ? 1 : 0;
-  ctx->knob_reset_align = knob("IPPM_RESET_ALIGN", 32);   // cells the reset's fill boxes are rounded outwards to (32 = a 128-byte line; 0: not)
-  if (ctx->knob_reset_align & (ctx->knob_reset_align - 1)) ctx->knob_reset_align = 32;
   ctx->knob_terrain_one_launch = knob("IPPM_TERRAIN_ONE_LAUNCH", 0);   // 1: ippm_terrain_truth's second pass as one launch (terrain.hip: measured, no gain)
-  ctx->knob_k3_dense = knob("IPPM_K3_DENSE", 1);   // 0: the power-of-two lane layout of round 3 (A/B: tools/ab_knobs.py)
   ctx->tiles = (ctx->vec == 4 && c.logit_prior == 0.f && c.grid_x < 32768 && c.grid_y <= 1024 && !knob("IPPM_NO_TILES", 0)) ? 1 : 0;
   // tile storage of the maps (ippm_set_map_layout); IPPM_MAP_TILED=1 turns it on at creation where the configuration can take it
   ctx->tl = (knob("IPPM_MAP_TILED", 0) > 0 && ippm_tile_storage_ok(ctx)) ? 1 : 0;
@@ -317,12 +295,3 @@ extern "C" int ippm_read_counters(ippm_ctx* ctx, ippm_counters* out, int reset, 
   if (reset) IPPM_HIP(hipMemset(ctx->dcounters, 0, sizeof(raw)));
   return 0;
 }
-
-#ifdef IPPM_PLAN_STAMPS
-// variant builds only: the raw counter slots (word 7 of each slot holds a phase stamp of k_plan_step's env 0)
-extern "C" int ippm_debug_raw_counters(ippm_ctx* ctx, unsigned long long* out512) {
-  IPPM_HIP(hipDeviceSynchronize());
-  IPPM_HIP(hipMemcpy(out512, ctx->dcounters, IPPM_COUNTER_SLOTS * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  return 0;
-}
-#endif

@@ -3,7 +3,6 @@
 // and the target-class F1 counts.  The per-candidate reduction streams a footprint tile of the agent's local map
 // exactly like K3 does (4 grid-aligned cells per lane), accumulates in float64 and is deterministic (no atomics), so
 // candidates with identical cell multisets get bit-identical gains and argmax ties resolve like the reference's.
-#include <cstdlib>
 
 #include "ippm_internal.h"
 
@@ -278,7 +277,7 @@ extern "C" int ippm_ig_candidates(ippm_ctx* ctx, const float* local, const int32
   const int total = n_envs * ctx->cfg.n_agents * ctx->cfg.n_actions;
   if (total <= 0) return 0;
   const int A = ctx->cfg.n_actions;
-  if ((A == 9 || A == 27) && ctx->cfg.grid_y >= 4 && !getenv("IPPM_IG_PER_CANDIDATE"))   // 3 x 3 sets: one walk of the hull per layer
+  if ((A == 9 || A == 27) && ctx->cfg.grid_y >= 4)   // 3 x 3 sets: one walk of the hull per layer
     hipLaunchKernelGGL(k_ig_union, dim3(n_envs * ctx->cfg.n_agents * (A / 9)), dim3(256), 0, S_(stream), ctx->dcfg, local, pos, mask, gains, ctx->tl);
   else
     hipLaunchKernelGGL(k_ig_candidates, dim3(total), dim3(256), 0, S_(stream), ctx->dcfg, local, pos, mask, gains, ctx->tl);

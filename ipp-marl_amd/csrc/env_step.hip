@@ -7,7 +7,6 @@
 //   - narrow footprints pack several rows into one 64-lane wavefront (lanes-per-row = next pow2);
 //   - every map cell is read and written at most once per kernel, whatever the number of fused measurements.
 #include <algorithm>
-#include <cstdlib>
 
 #include "ippm_tiles.h"
 
@@ -297,21 +296,9 @@ k_sense_update(const ippm_config* __restrict__ c, const int64_t* __restrict__ ep
 typedef unsigned ippm_k3_u4 __attribute__((ext_vector_type(4)));
 #define IPPM_K3_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
 #define IPPM_K3_OOB 0x7FFFFFF0
-#ifndef IPPM_K3_WAVES      // wavefronts per workgroup of k_sense_tiles (variant builds: 2 / 8)
-#define IPPM_K3_WAVES 4
-#endif
-#ifndef IPPM_K3_CH         // loads in flight per lane of k_sense_tiles (variant builds)
-#define IPPM_K3_CH 3
-#endif
-#ifndef IPPM_K3_GRID_ORDER // default workgroup order of k_sense_tiles (template parameter GO)
-#define IPPM_K3_GRID_ORDER 0
-#endif
-#ifndef IPPM_K3_LOAD_AUX   // cache policy of the map accesses (bit 1 = non-temporal on gfx950)
-#define IPPM_K3_LOAD_AUX 0
-#endif
-#ifndef IPPM_K3_STORE_AUX
-#define IPPM_K3_STORE_AUX 0
-#endif
+#define IPPM_K3_WAVES 4       // wavefronts per workgroup of k_sense_tiles
+#define IPPM_K3_CH 3          // loads in flight per lane of k_sense_tiles
+#define IPPM_K3_GRID_ORDER 0  // default workgroup order of k_sense_tiles (template parameter GO)
 
 // MIS: the grid is not a multiple of 4 wide (rows only 4-byte aligned); FLIPS: explicit flip tiles (parity mode) instead of Philox;
 // REC: rect_in holds K1's sense records (the closing kernel of a batched step) -- without it the footprint and the sensor constants
@@ -341,11 +328,10 @@ k_sense_tiles(const int32_t* __restrict__ rect_in, int n, int agent_sel, int sta
   // nothing else, and every config scalar the kernel uses is passed by value -- one scalar round trip, then the map loads.
   constexpr int CH = CHN;
   // grid = (row parts, agents, envs): no index arithmetic to undo
-  // (GO == 2, variant builds: the parts slowest -- all first parts, then all second parts, ...: 37 us at config 2 against 34)
   // (GO == 3, round 5, removed: every workgroup of an env on ONE XCD -- x = (env % 8) + 8 * agent, y = part, z = env / 8, so that the
   //  parts of a footprint share one L2's truth and code-tile lines, on the XCD the fusion's wavefronts of that env run on: 36.2 us
   //  against 34.7 at 256^2, 68.5 / 62.8 at 512^2, 110 / 94 at 1024^2 -- spreading a footprint over the XCDs is what it wants)
-  const int part = GO == 1 ? blockIdx.y : (GO == 2 ? blockIdx.z : blockIdx.x), e = GO == 2 ? blockIdx.y : blockIdx.z;
+  const int part = GO == 1 ? blockIdx.y : blockIdx.x, e = blockIdx.z;
   const int agent_blk = GO == 0 ? blockIdx.y : blockIdx.x;
   const int i = agent_sel >= 0 ? agent_sel : agent_blk;
   const int tile = e * n + agent_blk;
@@ -475,11 +461,11 @@ k_sense_tiles(const int32_t* __restrict__ rect_in, int n, int agent_sel, int sta
         cellv[q] = cell; rowv[q] = row; yv[q] = y;
         if (!TL) poff[q] = cell * 4;
         if (VEC == 4) {
-          const ippm_k3_u4 t = __builtin_amdgcn_raw_buffer_load_b128(rmap, on[q] ? poff[q] : IPPM_K3_OOB, 0, IPPM_K3_LOAD_AUX);
+          const ippm_k3_u4 t = __builtin_amdgcn_raw_buffer_load_b128(rmap, on[q] ? poff[q] : IPPM_K3_OOB, 0, 0);
           m[q].v[0] = __uint_as_float(t.x); m[q].v[1 % VEC] = __uint_as_float(t.y);
           m[q].v[2 % VEC] = __uint_as_float(t.z); m[q].v[3 % VEC] = __uint_as_float(t.w);
         } else {
-          m[q].v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmap, on[q] ? cell * 4 : IPPM_K3_OOB, 0, IPPM_K3_LOAD_AUX));
+          m[q].v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmap, on[q] ? cell * 4 : IPPM_K3_OOB, 0, 0));
         }
         // (grids not a multiple of 4 wide: a group's four truth bits may straddle a byte -- two bytes at any byte address)
         tw[q] = mis ? (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rtruth, on[q] ? (cell >> 3) : IPPM_K3_OOB, 0, 0)
@@ -547,14 +533,14 @@ k_sense_tiles(const int32_t* __restrict__ rect_in, int n, int agent_sel, int sta
           t.z = __float_as_uint(m[q].v[2 % VEC]); t.w = __float_as_uint(m[q].v[3 % VEC]);
           // the last group of a row that is not a multiple of 4 wide hangs over into the next row: its cells go out one by one
           const bool tail = mis && y + 4 > gy;
-          __builtin_amdgcn_raw_buffer_store_b128(t, rmap, tail ? IPPM_K3_OOB : off, 0, IPPM_K3_STORE_AUX);
+          __builtin_amdgcn_raw_buffer_store_b128(t, rmap, tail ? IPPM_K3_OOB : off, 0, 0);
           if (mis) {
-            __builtin_amdgcn_raw_buffer_store_b32(t.x, rmap, tail ? off : IPPM_K3_OOB, 0, IPPM_K3_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b32(t.y, rmap, tail && y + 1 < gy ? off + 4 : IPPM_K3_OOB, 0, IPPM_K3_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b32(t.z, rmap, tail && y + 2 < gy ? off + 8 : IPPM_K3_OOB, 0, IPPM_K3_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b32(t.x, rmap, tail ? off : IPPM_K3_OOB, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(t.y, rmap, tail && y + 1 < gy ? off + 4 : IPPM_K3_OOB, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(t.z, rmap, tail && y + 2 < gy ? off + 8 : IPPM_K3_OOB, 0, 0);
           }
         } else {
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(m[q].v[0]), rmap, off, 0, IPPM_K3_STORE_AUX);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(m[q].v[0]), rmap, off, 0, 0);
         }
         // (a group outside the footprint's columns -- rounded row segments -- has no byte in the code tile)
         __builtin_amdgcn_raw_buffer_store_b8((unsigned char)obs, rcode, on[q] && inm != 0 ? (int)tile_index<VEC>(row, y - tile_y0, S) : IPPM_K3_OOB, 0, 0);
@@ -587,9 +573,8 @@ k_sense_tiles(const int32_t* __restrict__ rect_in, int n, int agent_sel, int sta
 // start footprint in K3's dense lane geometry (a 90-cell footprint row = 3 passes of 8 lanes; a row-per-wavefront layout would
 // run the Philox rounds on 23 of 64 lanes), writing whole groups -- measured cells and the prior cells that share their groups.
 // ------------------------------------------------------------------------------------------------------
-#ifndef IPPM_RESET_ROWS
 #define IPPM_RESET_ROWS 32   // rows per FILL workgroup = 4 wavefronts x 8 rows.  One row per wavefront ran at the pace of wavefront
-#endif                       // launches (1.4 M of them: 310 us for 0.9 GB); 8 / 16 / 32 rows per workgroup: 201 / 180 / 148 us
+                             // launches (1.4 M of them: 310 us for 0.9 GB); 8 / 16 / 32 rows per workgroup: 201 / 180 / 148 us
 __global__ void __launch_bounds__(256)
 k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ episode, const int32_t* __restrict__ pos,
              const uint8_t* __restrict__ truth, float* __restrict__ local, float* __restrict__ global, const uint8_t* __restrict__ flips,
@@ -820,11 +805,6 @@ k_weighted_entropy(const ippm_config* __restrict__ c, const float* __restrict__ 
 // ======================================================================================================
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int grid1(size_t n, int b = 256) { return (int)((n + b - 1) / b); }
-// tuning knob (row splits per tile/map); the defaults are the measured best on MI355X
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
 
 static int fill_f32(ippm_ctx* ctx, float* p, float v, size_t n, hipStream_t st) {
   if (n == 0) return 0;
@@ -878,7 +858,7 @@ extern "C" int ippm_reset_maps(ippm_ctx* ctx, const int64_t* episode, const int3
   const int fill_chunks = (c.grid_x + IPPM_RESET_ROWS - 1) / IPPM_RESET_ROWS, sense_parts = ctx->tl ? ((h_max + 3) / 4 + 1 + 7) / 8 : (h_max + 31) / 32;
   dim3 grid((unsigned)(fill_chunks + sense_parts), (unsigned)(c.n_agents + 1), (unsigned)n_envs);
   IPPM_LAUNCH(ctx, IPPM_T_RESET_MAPS, k_reset_maps, grid, dim3(256), S_(stream), ctx->dcfg, episode, pos, truth, local, global, flips, code, rect,
-              ws, full ? 1 : 0, fill_chunks, ctx->n_active, (c.grid_y % 32 == 0 && !ctx->tl) ? ctx->knob_reset_align : 0, ctx->slabs, ippm_slab_count(ctx), ctx->tl);
+              ws, full ? 1 : 0, fill_chunks, ctx->n_active, (c.grid_y % 32 == 0 && !ctx->tl) ? 32 : 0, ctx->slabs, ippm_slab_count(ctx), ctx->tl);
   IPPM_LAUNCH_CHECK("reset_maps");
   return 0;
 }
@@ -963,107 +943,82 @@ extern "C" int ippm_sense_step(ippm_ctx* ctx, const int64_t* episode, const int3
   if (agent_sel >= ctx->cfg.n_agents) { ippm_set_error("ippm_sense_update: agent_sel out of range"); return -1; }
   if ((sums == nullptr) != (reward == nullptr)) { ippm_set_error("ippm_sense_step: sums and reward go together"); return -1; }
   if (n_envs <= 0) return 0;
-  const int maps = agent_sel >= 0 ? n_envs : n_envs * ctx->cfg.n_agents;
-  const int tail = sums ? grid1(n_envs) : 0;
-  dim3 block(256);
-  if ((!area || ctx->vec == 4) && (ctx->tl || !env_int("IPPM_K3_CLASSIC", 0))) {
-    // tile form: one trip per workgroup for the common footprints (rows_per_part = 4 wavefronts x 8 rows); with the area sums
-    // tracked in its TRACK instantiation (16-byte layout only: k_sense_update below keeps the narrow grids)
-    const ippm_config& c = ctx->cfg;
-    int h_max = 1;
-    for (int k = 0; k < c.space_z; ++k) h_max = std::max(h_max, 2 * c.radius_x[k]);
-    // workgroup shape: wavefronts per workgroup x loads in flight per lane.  (4, 3) unless the production combination below runs
-    // with another one (knobs IPPM_K3_WPG / IPPM_K3_CHN, or the per-grid-width choice of ippm_ctx_create)
-    int wpg = IPPM_K3_WAVES, chn = IPPM_K3_CH;
-    const bool shaped = ctx->vec == 4 && !flips && rect_in && !area && (c.grid_y & 3) == 0 && ctx->knob_k3_dense != 0;
-    if (shaped) { wpg = ctx->k3_wpg; chn = ctx->k3_chn; }
-    const int rows_per_part = std::max(4, env_int("IPPM_K3_ROWS", 8 * wpg));
-    block = dim3(64 * wpg);
-    int parts = (h_max + rows_per_part - 1) / rows_per_part;
-    // dense lane mapping (k_sense_tiles<..., DENSE>): a part is a run of wpg * chn * 64 of the footprint's row-major 4-cell groups
-    // (W per row: one more than its width needs when it starts off a group boundary)
-    const bool tl = ctx->tl != 0;     // tile storage (ippm_set_map_layout): always the dense form
-    const bool dense = ctx->vec == 4 && (ctx->knob_k3_dense != 0 || tl);
-    // row segments rounded outwards to whole 128-byte lines (k_sense_tiles): dense form, rows a multiple of 32 cells long; on by default for
-    // rows of at least 512 cells (IPPM_K3_ROUND forces it on / off) -- profiles/r06/tile_round_ab.txt
-    const int col_round = (dense && !tl && (c.grid_y % 32) == 0 && ctx->knob_k3_round > 0) ? ippm_round_cells(ctx->knob_k3_round) : 4;
-    if (dense && tl) {
-      int need = 1;    // lane-loads of the largest footprint's tiles: rows of tiles x 8 per tile, one more of either than its size needs
-      for (int k = 0; k < c.space_z; ++k) {
-        const int ht = std::min(c.grid_x / 4, (2 * c.radius_x[k] + 3) / 4 + 1), wt = std::min(c.grid_y / 8, (2 * c.radius_y[k] + 7) / 8 + 1);
-        need = std::max(need, (ht * wt * 8 + wpg * chn * 64 - 1) / (wpg * chn * 64));
-      }
-      parts = need;
-    } else if (dense) {
-      int need = 1;
-      for (int k = 0; k < c.space_z; ++k) {
-        int wmax = (2 * c.radius_y[k] + 3) / 4 + 1;
-        if (col_round > 4) wmax = std::min((c.grid_y + 3) / 4, (wmax + 2 * (col_round / 4 - 1) + col_round / 4 - 1) / (col_round / 4) * (col_round / 4));   // rounded row segments
-        need = std::max(need, (2 * c.radius_x[k] * wmax + wpg * chn * 64 - 1) / (wpg * chn * 64));
-      }
-      parts = need;
+  int32_t* rect_out = rect_in == rect ? nullptr : rect;
+  const ippm_config& c = ctx->cfg;
+  if (area && ctx->vec == 1) {
+    // narrow grids (one cell per lane) with the area sums tracked: a footprint's rows in two workgroups, and ceil(E / 256) more
+    // workgroups behind them for the reward of the step's global fusion
+    const int split = 2;
+    const int maps = agent_sel >= 0 ? n_envs : n_envs * c.n_agents;
+    const int tail = sums ? grid1(n_envs) : 0;
+    dim3 grid((unsigned)maps * split + tail);
+    IPPM_LAUNCH(ctx, IPPM_T_SENSE, (k_sense_update<1, 1, true>), grid, dim3(256), S_(stream), ctx->dcfg, episode, pos, truth, local, flips, code,
+                rect_in, rect_out, ws, area, sums, reward, ctx->dcounters, stage, agent_sel, split, maps, n_envs, ctx->n_active);
+    IPPM_LAUNCH_CHECK("sense_update");
+    return 0;
+  }
+  // tile form: one trip per workgroup for the common footprints (rows_per_part = 8 rows per wavefront); with the area sums
+  // tracked in its TRACK instantiation (16-byte layout only: k_sense_update above keeps the narrow grids)
+  if (n_envs > 65535) { ippm_set_error("ippm_sense_step: more than 65535 envs per launch"); return -1; }
+  int h_max = 1;
+  for (int k = 0; k < c.space_z; ++k) h_max = std::max(h_max, 2 * c.radius_x[k]);
+  // workgroup shape and order: (4 wavefronts, 3 loads in flight per lane, a footprint's parts first) unless this is the closing K3 of
+  // the env-only step, which takes the per-grid-width choice of ippm_resolve_k3_shape (api.hip)
+  int wpg = IPPM_K3_WAVES, chn = IPPM_K3_CH, go = IPPM_K3_GRID_ORDER;
+  const bool shaped = ctx->vec == 4 && !flips && rect_in && !area && (c.grid_y & 3) == 0;
+  if (shaped) { wpg = ctx->k3_wpg; chn = ctx->k3_chn; go = ctx->k3_go; }
+  const int rows_per_part = 8 * wpg;
+  int parts = (h_max + rows_per_part - 1) / rows_per_part;
+  // dense lane mapping (k_sense_tiles<..., DENSE>; the 16-byte layout always, tile storage included): a part is a run of wpg * chn * 64
+  // of the footprint's row-major 4-cell groups (W per row: one more than its width needs when it starts off a group boundary)
+  const bool tl = ctx->tl != 0;     // tile storage (ippm_set_map_layout)
+  const bool dense = ctx->vec == 4;
+  // row segments rounded outwards to whole 128-byte lines (k_sense_tiles): dense form, rows a multiple of 32 cells long and at least
+  // 512 cells -- profiles/r06/tile_round_ab.txt
+  const int col_round = (dense && !tl && (c.grid_y % 32) == 0 && c.grid_y >= 512) ? 32 : 4;
+  if (dense && tl) {
+    int need = 1;    // lane-loads of the largest footprint's tiles: rows of tiles x 8 per tile, one more of either than its size needs
+    for (int k = 0; k < c.space_z; ++k) {
+      const int ht = std::min(c.grid_x / 4, (2 * c.radius_x[k] + 3) / 4 + 1), wt = std::min(c.grid_y / 8, (2 * c.radius_y[k] + 7) / 8 + 1);
+      need = std::max(need, (ht * wt * 8 + wpg * chn * 64 - 1) / (wpg * chn * 64));
     }
-    if (n_envs > 65535) { ippm_set_error("ippm_sense_step: more than 65535 envs per launch"); return -1; }
-    const unsigned g_agents = (unsigned)(agent_sel >= 0 ? 1 : c.n_agents);
-    const int go = shaped ? ctx->k3_go : IPPM_K3_GRID_ORDER;
-    dim3 grid = go == 1 ? dim3(g_agents, (unsigned)parts, (unsigned)n_envs)
-              : (go == 2 ? dim3(g_agents, (unsigned)n_envs, (unsigned)parts) : dim3((unsigned)parts, g_agents, (unsigned)n_envs));
-    int32_t* rect_out = rect_in == rect ? nullptr : rect;
-#define IPPM_K3T____(V, M, F, R, D, T, L, ...)                                                                                       \
+    parts = need;
+  } else if (dense) {
+    int need = 1;
+    for (int k = 0; k < c.space_z; ++k) {
+      int wmax = (2 * c.radius_y[k] + 3) / 4 + 1;
+      if (col_round > 4) wmax = std::min((c.grid_y + 3) / 4, (wmax + 2 * (col_round / 4 - 1) + col_round / 4 - 1) / (col_round / 4) * (col_round / 4));   // rounded row segments
+      need = std::max(need, (2 * c.radius_x[k] * wmax + wpg * chn * 64 - 1) / (wpg * chn * 64));
+    }
+    parts = need;
+  }
+  const unsigned g_agents = (unsigned)(agent_sel >= 0 ? 1 : c.n_agents);
+  const dim3 grid = go == 1 ? dim3(g_agents, (unsigned)parts, (unsigned)n_envs) : dim3((unsigned)parts, g_agents, (unsigned)n_envs);
+  const dim3 block(64 * wpg);
+  // k_sense_tiles<cells per lane, misaligned rows, explicit flips, sense records, dense, area sums, tile storage[, wavefronts, loads, order]>
+#define IPPM_K3(V, M, F, R, D, T, L, ...)                                                                                            \
   IPPM_LAUNCH(ctx, IPPM_T_SENSE, (k_sense_tiles<V, M, F, R, D, T, L __VA_OPT__(,) __VA_ARGS__>), grid, block, S_(stream), rect_in, c.n_agents, agent_sel, stage, rows_per_part, \
               c.grid_y, c.grid_x, local, truth, episode, code, c.tile_stride, c.logit_clip, (uint32_t)c.philox_seed,                 \
               (uint32_t)(c.philox_seed >> 32), ctx->dcfg, pos, flips, rect_out, ws, sums, reward, ctx->dcounters, area, ctx->n_active, col_round)
-#define IPPM_K3T___(V, M, F, R, D, T, ...) IPPM_K3T____(V, M, F, R, D, T, false __VA_OPT__(,) __VA_ARGS__)
-#define IPPM_K3T__(V, M, F, R, D) do { if (area) IPPM_K3T___(V, M, F, R, D, true); else IPPM_K3T___(V, M, F, R, D, false); } while (0)
-#define IPPM_K3TL_(F, R) do { if (area) IPPM_K3T____(4, false, F, R, true, true, true); else IPPM_K3T____(4, false, F, R, true, false, true); } while (0)
-#define IPPM_K3TL(F) do { if (rect_in) IPPM_K3TL_(F, true); else IPPM_K3TL_(F, false); } while (0)
-#define IPPM_K3T_(V, M, F, R) do { if (dense) IPPM_K3T__(V, M, F, R, true); else IPPM_K3T__(V, M, F, R, false); } while (0)
-#define IPPM_K3T(V, M, F) do { if (rect_in) IPPM_K3T_(V, M, F, true); else IPPM_K3T_(V, M, F, false); } while (0)
-    if (shaped && !(wpg == IPPM_K3_WAVES && chn == IPPM_K3_CH && go == IPPM_K3_GRID_ORDER)) {   // the closing K3 of the env-only step in another workgroup shape / order
-#define IPPM_K3S(W_, C_, G_) if (wpg == W_ && chn == C_ && go == G_) { \
-        if (tl) IPPM_K3T____(4, false, false, true, true, false, true, W_, C_, G_); else IPPM_K3T____(4, false, false, true, true, false, false, W_, C_, G_); \
-        IPPM_LAUNCH_CHECK("sense_tiles"); return 0; }
-      IPPM_K3S(2, 2, 1) IPPM_K3S(2, 2, 0) IPPM_K3S(1, 3, 0) IPPM_K3S(2, 3, 0) IPPM_K3S(1, 4, 0) IPPM_K3S(2, 4, 0) IPPM_K3S(4, 4, 0) IPPM_K3S(4, 2, 0) IPPM_K3S(4, 3, 1)
-#undef IPPM_K3S
-      ippm_set_error("ippm_sense_step: no instantiation for this K3 shape (IPPM_K3_WPG x IPPM_K3_CHN)");
-      return -1;
-    }
-    const bool mis = (c.grid_y & 3) != 0;
-    if (tl) {
-      if (flips) IPPM_K3TL(true); else IPPM_K3TL(false);
-    } else if (ctx->vec == 4) {
-      if (flips) { if (mis) IPPM_K3T(4, true, true); else IPPM_K3T(4, false, true); }
-      else { if (mis) IPPM_K3T(4, true, false); else IPPM_K3T(4, false, false); }
-    } else {
-      if (flips) IPPM_K3T___(1, false, true, false, false, false); else IPPM_K3T___(1, false, false, false, false, false);
-    }
-#undef IPPM_K3T____
-#undef IPPM_K3T___
-#undef IPPM_K3TL_
-#undef IPPM_K3TL
-#undef IPPM_K3T__
-#undef IPPM_K3T_
-#undef IPPM_K3T
-    IPPM_LAUNCH_CHECK("sense_tiles");
-    return 0;
-  }
-  const int split = std::max(1, env_int("IPPM_SPLIT_K3", 2));
-  dim3 grid((unsigned)maps * split + tail);
-  const int unr = env_int("IPPM_UNROLL_K3", 2);
-  int32_t* rect_out = rect_in == rect ? nullptr : rect;
-#define IPPM_K3_LAUNCH(V, U, T)                                                                                               \
-  IPPM_LAUNCH(ctx, IPPM_T_SENSE, (k_sense_update<V, U, T>), grid, block, S_(stream), ctx->dcfg, episode, pos, truth, local, flips, code, \
-              rect_in, rect_out, ws, area, sums, reward, ctx->dcounters, stage, agent_sel, split, maps, n_envs, ctx->n_active)
-  if (ctx->vec == 4) {
-    if (area) { if (unr >= 2) IPPM_K3_LAUNCH(4, 2, true); else IPPM_K3_LAUNCH(4, 1, true); }
-    else if (unr >= 4) IPPM_K3_LAUNCH(4, 4, false);
-    else if (unr >= 2) IPPM_K3_LAUNCH(4, 2, false);
-    else IPPM_K3_LAUNCH(4, 1, false);
-  } else {
-    if (area) IPPM_K3_LAUNCH(1, 1, true); else IPPM_K3_LAUNCH(1, 1, false);
-  }
-#undef IPPM_K3_LAUNCH
-  IPPM_LAUNCH_CHECK("sense_update");
+  // the 16-byte dense form by what the call brings: area sums, sense records, explicit flips
+#define IPPM_K3_T(M, F, R, L) do { if (area) IPPM_K3(4, M, F, R, true, true, L); else IPPM_K3(4, M, F, R, true, false, L); } while (0)
+#define IPPM_K3_R(M, F, L) do { if (rect_in) IPPM_K3_T(M, F, true, L); else IPPM_K3_T(M, F, false, L); } while (0)
+#define IPPM_K3_F(M, L) do { if (flips) IPPM_K3_R(M, true, L); else IPPM_K3_R(M, false, L); } while (0)
+  const bool mis = (c.grid_y & 3) != 0;
+  if (shaped && tl && wpg == 1 && chn == 3 && go == 0) IPPM_K3(4, false, false, true, true, false, true, 1, 3, 0);
+  else if (shaped && tl && wpg == 2 && chn == 2 && go == 0) IPPM_K3(4, false, false, true, true, false, true, 2, 2, 0);
+  else if (shaped && !tl && wpg == 2 && chn == 2 && go == 1) IPPM_K3(4, false, false, true, true, false, false, 2, 2, 1);
+  else if (shaped && !tl && wpg == 2 && chn == 2 && go == 0) IPPM_K3(4, false, false, true, true, false, false, 2, 2, 0);
+  else if (tl) IPPM_K3_F(false, true);             // (from here on the default shape: 4 wavefronts, 3 loads, parts first)
+  else if (ctx->vec == 4 && mis) IPPM_K3_F(true, false);
+  else if (ctx->vec == 4) IPPM_K3_F(false, false);
+  else if (flips) IPPM_K3(1, false, true, false, false, false, false);
+  else IPPM_K3(1, false, false, false, false, false, false);
+#undef IPPM_K3_F
+#undef IPPM_K3_R
+#undef IPPM_K3_T
+#undef IPPM_K3
+  IPPM_LAUNCH_CHECK("sense_tiles");
   return 0;
 }
 

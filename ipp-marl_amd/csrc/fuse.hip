@@ -22,7 +22,6 @@
 // issue-bound at 13 % of the HBM peak.  (It also taught that per-cell selects on loop-invariant masks get hoisted into
 // saved-exec branches by the compiler, 5x slower again: IPPM_OPAQUE below.)
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "ippm_tiles.h"
@@ -72,20 +71,14 @@ struct WaveAcc {
 
 // (entropy_l_f64, the SHIFT path's float64 entropy: ippm_internal.h, shared with k_agent_rewards)
 
-#ifndef IPPM_FUSE_LOAD_AUX   // cache policy of the map accesses (bit 1 = non-temporal on gfx950)
-#define IPPM_FUSE_LOAD_AUX 0
-#endif
-#ifndef IPPM_FUSE_STORE_AUX
-#define IPPM_FUSE_STORE_AUX 0
-#endif
 template <int VEC>
 __device__ __forceinline__ CellVec<VEC> buf_load_cells(__amdgpu_buffer_rsrc_t r, int off) {
   CellVec<VEC> c;
   if (VEC == 4) {
-    const ippm_u4 t = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, IPPM_FUSE_LOAD_AUX);
+    const ippm_u4 t = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
     c.v[0] = __uint_as_float(t.x); c.v[1 % VEC] = __uint_as_float(t.y); c.v[2 % VEC] = __uint_as_float(t.z); c.v[3 % VEC] = __uint_as_float(t.w);
   } else {
-    c.v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, IPPM_FUSE_LOAD_AUX));
+    c.v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
   }
   return c;
 }
@@ -94,9 +87,9 @@ __device__ __forceinline__ void buf_store_cells(__amdgpu_buffer_rsrc_t r, int of
   if (VEC == 4) {
     ippm_u4 t;
     t.x = __float_as_uint(c.v[0]); t.y = __float_as_uint(c.v[1 % VEC]); t.z = __float_as_uint(c.v[2 % VEC]); t.w = __float_as_uint(c.v[3 % VEC]);
-    __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, IPPM_FUSE_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, 0);
   } else {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c.v[0]), r, off, 0, IPPM_FUSE_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c.v[0]), r, off, 0, 0);
   }
 }
 
@@ -170,12 +163,7 @@ __device__ __forceinline__ void walk_slab(const WaveCtx& w, const OpTable& t, Wa
     const int ycode = VEC == 4 ? (y >> 2) : y;
     const int ybyte = y * 4, gybyte = w.gy * 4;
     float amax = 0.f;
-#ifdef IPPM_X_NOROWS
-    amax = (float)(cshift[0] + cm[0] + cm[NA - 1]) + lm0[0] + lm1[NA - 1] + (float)keepm;
-    for (int row0 = rs; row0 < rs; row0 += FU) {
-#else
     for (int row0 = rs; row0 < re; row0 += FU) {
-#endif
       // issue every load of FU rows (map cells + one measurement-code byte per slot) before any use
       CellVec<VEC> mvu[FU];
       uint32_t cwu[FU][NA];
@@ -206,7 +194,6 @@ __device__ __forceinline__ void walk_slab(const WaveCtx& w, const OpTable& t, Wa
         // grid (mappings.py:110-111), then adds the measurement's log-odds inside its footprint.  So every cell this lane
         // holds may be clipped at every op, covered or not (for an uncovered cell that is the reference's own full-grid
         // clip; the deferred-clamp plan guarantees it is a no-op there); only the addend is masked to the footprint.
-#ifndef IPPM_X_NOCHAIN
 #pragma unroll
         for (int k = 0; k < NA; ++k) {
           const uint32_t cw = cwu[u][k];
@@ -217,9 +204,6 @@ __device__ __forceinline__ void walk_slab(const WaveCtx& w, const OpTable& t, Wa
             else L[q] = ippm_clampl((float)L[q], w.lc) + lm;
           }
         }
-#else
-        for (int k = 0; k < NA; ++k) L[0] += __uint_as_float(cwu[u][k]);
-#endif
         // outputs of the plan's last op stay unclamped (its rectangle is remembered as possibly out of range); every other
         // cell was clipped again by a later op of the reference
         float d[VEC];
@@ -238,15 +222,14 @@ __device__ __forceinline__ void walk_slab(const WaveCtx& w, const OpTable& t, Wa
             // out one by one, another lane owns the rest
             const bool tail = y + 4 > w.gy;
             buf_store_cells<VEC>(w.map, tail ? 0x7FFFFFF0 : soff, mv);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[0]), w.map, tail ? soff : 0x7FFFFFF0, 0, IPPM_FUSE_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[1 % VEC]), w.map, tail && y + 1 < w.gy ? soff + 4 : 0x7FFFFFF0, 0, IPPM_FUSE_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[2 % VEC]), w.map, tail && y + 2 < w.gy ? soff + 8 : 0x7FFFFFF0, 0, IPPM_FUSE_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[0]), w.map, tail ? soff : 0x7FFFFFF0, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[1 % VEC]), w.map, tail && y + 1 < w.gy ? soff + 4 : 0x7FFFFFF0, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[2 % VEC]), w.map, tail && y + 2 < w.gy ? soff + 8 : 0x7FFFFFF0, 0, 0);
           } else {
             buf_store_cells<VEC>(w.map, soff, mv);
           }
         }
         if (TRACK) area_row<VEC>(acc, w.s_area, ac, min(row, re - 1), w.gx, w.inv_gx, d);
-#ifndef IPPM_X_NOREWARD
         if (w.is_global) {
           // information-gain terms (utils/reward.py:68-82); a cell that received no measurement contributes exact zeros
           // (same weight, and the entropy clips its argument).  Rows whose cells all have weight 0 before and after
@@ -277,7 +260,6 @@ __device__ __forceinline__ void walk_slab(const WaveCtx& w, const OpTable& t, Wa
             if (!SHIFT) { acc_out.a1 += (double)r1; acc_out.aD += (double)rD; }
           }
         }
-#endif
       }
     }
     acc_out.exceed |= amax > w.lc;
@@ -296,15 +278,9 @@ __device__ __forceinline__ void walk_slab(const WaveCtx& w, const OpTable& t, Wa
   }
 }
 
-#ifndef IPPM_FU_SMALL
 #define IPPM_FU_SMALL 2  // rows in flight per lane in the row loops for 1-2 active ops
-#endif
-#ifndef IPPM_FU_MID
 #define IPPM_FU_MID 2    // ... for 3-4 active ops
-#endif
-#ifndef IPPM_FU_BIG
 #define IPPM_FU_BIG 1    // ... for more
-#endif
 
 // One work item = (map, run of `wave_rows` consecutive rows of the map's op hull), done by one wavefront.
 // NAMAX = plan-size class of the launch (6 / 10 / 18): the row loops compiled in are those for <= NAMAX active ops.
@@ -459,9 +435,7 @@ __device__ __forceinline__ void fuse_item(const ippm_config* __restrict__ c, flo
 //                  (item = map << 8 | run); the launch is a fixed number of wavefronts, a few per env, that stride over their
 //                  env's items, so hardly a slot is spent on an empty item and no "round" of short-lived workgroups has to
 //                  drain before the next.
-#ifndef IPPM_FUSE_WAVES
 #define IPPM_FUSE_WAVES 4
-#endif
 template <int VEC, bool TRACK, int NAMAX, bool SHIFT>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(IPPM_FUSE_WAVES, 8)))
 k_fuse_rows(const ippm_config* __restrict__ c, float* __restrict__ local, float* __restrict__ global,
@@ -520,13 +494,9 @@ static inline int grid1(size_t n, int b = 256) { return (int)((n + b - 1) / b); 
 // same parallelism with shorter per-wavefront latency chains.
 int ippm_fuse_wave_rows(const ippm_ctx* ctx, int n_envs) {
   const int gx = ctx->cfg.grid_x;
-  const int forced = ctx->knob_wave_rows;  // IPPM_FUSE_WAVE_ROWS, read at ippm_ctx_create
-  int rows = forced;
-  if (rows <= 0) {
-    const double est_rows = 0.5 * (double)n_envs * (ctx->cfg.n_agents + 1) * 0.6 * gx;
-    rows = 8;
-    while (rows < 32 && est_rows / rows > 12288.0 * 1.5) rows *= 2;   // (64 rows per item: 5 % slower at 8 UAVs x 512^2)
-  }
+  const double est_rows = 0.5 * (double)n_envs * (ctx->cfg.n_agents + 1) * 0.6 * gx;
+  int rows = 8;
+  while (rows < 32 && est_rows / rows > 12288.0 * 1.5) rows *= 2;   // (64 rows per item: 5 % slower at 8 UAVs x 512^2)
   return std::min(gx, std::max((gx + 255) / 256, rows));
 }
 
@@ -545,7 +515,7 @@ static int launch_fuse(ippm_ctx* ctx, float* local, float* global, const uint8_t
   // ... and about three items per wavefront on larger grids / teams (8 UAVs x 512^2 x 1024 envs: 16 / 32 / 64 wavefronts per env
   // -> 1211 / 1173 / 1234 us; 4 UAVs x 1024^2: 16 / 64 -> 1577 / 1477 us)
   const int per_env = ((c.n_agents + 1) * chunks + 2) / 3;
-  const int persist = std::max(64, ctx->knob_persist > 0 ? ctx->knob_persist : std::max(16384, per_env * n_envs_total));
+  const int persist = std::max(16384, per_env * n_envs_total);
   const int pgrid = n_envs_total * std::max(1, std::min(persist / std::max(n_envs_total, 1), (c.n_agents + 1) * chunks));
   dim3 grid(work ? (unsigned)pgrid : (unsigned)units * chunks), block(64);
 #define IPPM_FUSE(V, T, NA, SH, MINOPS)                                                                                  \
@@ -615,14 +585,9 @@ extern "C" int ippm_fuse_global_reward(ippm_ctx* ctx, float* global, const uint8
 extern "C" int ippm_fuse_step(ippm_ctx* ctx, float* local, float* global, const uint8_t* code, int32_t* ws, double* sums,
                               double* area, const int32_t* work, int32_t n_envs, void* stream) {
   if (!ctx || !local || !global || !code || !ws || !sums) { ippm_set_error("ippm_fuse_step: null argument"); return -1; }
-  // the work list may be in the one-trip tile form (ippm_plan_step with IPPM_STEP_TILES): fuse_tiles.hip; a list of the other
-  // form is skipped and counted by whichever kernel is handed it
-  if (work && ctx->tiles && !ctx->knob_nowork && !ctx->knob_split)
+  // the tile form if the context has it (the work list is then in the one-trip tile form, ippm_plan_step: fuse_tiles.hip), else the row
+  // walker with the work list; a list of the other form is skipped and counted by whichever kernel is handed it
+  if (work && ctx->tiles)
     return ippm_launch_fuse_tiles(ctx, local, global, code, ws, sums, area, work, n_envs, S_(stream));
-  if (ctx->knob_split) {  // measurement aid: K4 and K5 as two launches, so that a kernel trace shows them apart
-    if (int rc = launch_fuse(ctx, local, global, code, ws, sums, area, nullptr, n_envs * ctx->cfg.n_agents, 0, -1, n_envs, S_(stream))) return rc;
-    return launch_fuse(ctx, local, global, code, ws, sums, area, nullptr, 0, n_envs, -1, n_envs, S_(stream));
-  }
-  return launch_fuse(ctx, local, global, code, ws, sums, area, ctx->knob_nowork ? nullptr : work,
-                     n_envs * ctx->cfg.n_agents, n_envs, -1, n_envs, S_(stream));
+  return launch_fuse(ctx, local, global, code, ws, sums, area, work, n_envs * ctx->cfg.n_agents, n_envs, -1, n_envs, S_(stream));
 }

@@ -24,25 +24,7 @@
 typedef unsigned ippm_t_u4 __attribute__((ext_vector_type(4)));
 #define IPPM_T_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
 #define IPPM_T_OOB 0x7FFFFFF0
-#ifndef IPPM_T_LOAD_AUX    // cache policy of the map accesses (variant builds; bit 1 = non-temporal on gfx950)
-#define IPPM_T_LOAD_AUX 0
-#endif
-#ifndef IPPM_T_STORE_AUX
-#define IPPM_T_STORE_AUX 0
-#endif
 #define IPPM_T_FAR (-(1 << 20))   // column of a lane-load past the item's end: no op covers it
-// measurement-only variants (make VARIANT=... EXTRA=-DIPPM_X_...; results are wrong on purpose): what the launch takes without the
-// reward arithmetic (IPPM_X_NOREWARD), without the per-op clip-and-add (IPPM_X_NOCHAIN), without the code-byte loads (IPPM_X_NOCODE)
-#ifdef IPPM_X_NOREWARD
-#define IPPM_X_REWARD false
-#else
-#define IPPM_X_REWARD true
-#endif
-#ifdef IPPM_X_NOCODE
-#define IPPM_X_CODE(load) 0u
-#else
-#define IPPM_X_CODE(load) (load)
-#endif
 
 __device__ __forceinline__ int t_lane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 __device__ __forceinline__ float t_lane_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
@@ -179,7 +161,7 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
     xrow[q] = row;
     coff[q] = row * w.row_bytes + g;
     ycol[q] = valid ? g * 4 : IPPM_T_FAR;
-    const ippm_t_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rmap, off[q], 0, IPPM_T_LOAD_AUX);
+    const ippm_t_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rmap, off[q], 0, 0);
     mv[q].v[0] = __uint_as_float(v.x); mv[q].v[1] = __uint_as_float(v.y); mv[q].v[2] = __uint_as_float(v.z); mv[q].v[3] = __uint_as_float(v.w);
   }
   // ---- trip 3: one measurement-code byte per (slot, op)
@@ -187,7 +169,7 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
 #pragma unroll
   for (int q = 0; q < SLOTS; ++q)
 #pragma unroll
-    for (int k = 0; k < NA; ++k) cw[q][k] = IPPM_X_CODE(__builtin_amdgcn_raw_buffer_load_b8(rcode, coff[q] + cs[k], 0, 0));
+    for (int k = 0; k < NA; ++k) cw[q][k] = __builtin_amdgcn_raw_buffer_load_b8(rcode, coff[q] + cs[k], 0, 0);
   // ---- the ordered clamp/add chain (mappings.py:80-124 in log-odds): every op clips its input over the whole grid
   // (mappings.py:110-111), then adds the measurement's log-odds inside its footprint; the outputs of the plan's last op stay
   // unclamped (its rectangle is remembered as possibly out of range), every other cell was clipped again by a later op.
@@ -211,15 +193,11 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
       keepm = k == keep_slot ? cm : keepm;
       opcells += (lm0 != 0.f || lm1 != 0.f) ? __popc(cm) : 0;
       const uint32_t cwk = cw[q][k];
-#ifndef IPPM_X_NOCHAIN
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float lm = ippm_masked(ippm_bitmask(cm, j), ippm_blend(ippm_bitmask(cwk, j), lm1, lm0));
         L[j] = ippm_clampl(L[j], w.lc) + lm;
       }
-#else
-      L[0] += __uint_as_float(cwk & 1u);   // (the code byte stays live)
-#endif
     }
     cells += __popc(touched);
     float out[4];
@@ -244,11 +222,11 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
         __builtin_amdgcn_raw_buffer_store_b32(v.y, rmap, tail && ycol[q] + 1 < w.gy ? off[q] + 4 : IPPM_T_OOB, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b32(v.z, rmap, tail && ycol[q] + 2 < w.gy ? off[q] + 8 : IPPM_T_OOB, 0, 0);
       } else {
-        __builtin_amdgcn_raw_buffer_store_b128(v, rmap, off[q], 0, IPPM_T_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(v, rmap, off[q], 0, 0);
       }
     }
     if (TRACK) tile_area_slot<MIS>(w, xrow[q], ycol[q] == IPPM_T_FAR ? 0 : ycol[q], mv[q].v, out);
-    if (IPPM_X_REWARD && is_global) {
+    if (is_global) {
       // information-gain terms (utils/reward.py:68-82) of the cells the step changed; an untouched cell contributes exact zeros
       // (same weight, same entropy).  Slots whose touched cells all have weight 0 before and after (believed free, still
       // believed free) skip the entropies: wave-uniform on spatially coherent terrain.
@@ -321,7 +299,7 @@ __device__ __forceinline__ void tile_item_long(const TileCtx& w, TileAcc& acc, i
     coff[q] = row * w.row_bytes + g;
     ycol[q] = valid ? g * 4 : IPPM_T_FAR;
     touched[q] = 0; keepm[q] = 0;
-    const ippm_t_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rmap, off[q], 0, IPPM_T_LOAD_AUX);
+    const ippm_t_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rmap, off[q], 0, 0);
     mv[q].v[0] = __uint_as_float(v.x); mv[q].v[1] = __uint_as_float(v.y); mv[q].v[2] = __uint_as_float(v.z); mv[q].v[3] = __uint_as_float(v.w);
   }
   // one op: its record (two 16-byte scalar loads) and its code byte per slot
@@ -339,7 +317,7 @@ __device__ __forceinline__ void tile_item_long(const TileCtx& w, TileAcc& acc, i
     o.lm1 = isf ? __int_as_float(b.w) : 0.f;
     const int cs = isf ? (e * w.n + a.y) * w.TB - b.y * w.row_bytes - (a.w >> 2) : 0;
 #pragma unroll
-    for (int q = 0; q < SLOTS; ++q) o.cw[q] = IPPM_X_CODE(__builtin_amdgcn_raw_buffer_load_b8(rcode, coff[q] + cs, 0, 0));
+    for (int q = 0; q < SLOTS; ++q) o.cw[q] = __builtin_amdgcn_raw_buffer_load_b8(rcode, coff[q] + cs, 0, 0);
   };
   OpIn cur, nxt;
   fetch(cur);
@@ -362,15 +340,11 @@ __device__ __forceinline__ void tile_item_long(const TileCtx& w, TileAcc& acc, i
       touched[q] |= cm;
       keepm[q] = is_last ? cm : keepm[q];
       opcells += (cur.lm0 != 0.f || cur.lm1 != 0.f) ? __popc(cm) : 0;
-#ifndef IPPM_X_NOCHAIN
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float lm = ippm_masked(ippm_bitmask(cm, j), ippm_blend(ippm_bitmask(cur.cw[q], j), cur.lm1, cur.lm0));
         L[q][j] = ippm_clampl(L[q][j], w.lc) + lm;
       }
-#else
-      L[q][0] += __uint_as_float(cur.cw[q] & 1u);
-#endif
     }
     if (!more) break;
     cur = nxt;
@@ -393,11 +367,11 @@ __device__ __forceinline__ void tile_item_long(const TileCtx& w, TileAcc& acc, i
         __builtin_amdgcn_raw_buffer_store_b32(v.y, rmap, tail && ycol[q] + 1 < w.gy ? off[q] + 4 : IPPM_T_OOB, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b32(v.z, rmap, tail && ycol[q] + 2 < w.gy ? off[q] + 8 : IPPM_T_OOB, 0, 0);
       } else {
-        __builtin_amdgcn_raw_buffer_store_b128(v, rmap, off[q], 0, IPPM_T_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(v, rmap, off[q], 0, 0);
       }
     }
     if (TRACK) tile_area_slot<MIS>(w, xrow[q], ycol[q] == IPPM_T_FAR ? 0 : ycol[q], mv[q].v, out);
-    if (IPPM_X_REWARD && is_global) {   // the reward terms, as in tile_item
+    if (is_global) {   // the reward terms, as in tile_item
       float wa[4], wb[4], wsum = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -429,15 +403,11 @@ __device__ __forceinline__ void tile_item_long(const TileCtx& w, TileAcc& acc, i
 // first + gridDim.y, ... of the env's list (which env a workgroup serves: blockIdx.x, rotated with `first` -- see the kernel).
 // (wavefronts per SIMD: the untracked instantiation fits in 80 VGPRs without scratch and takes 6 -- for every team size since
 // round 5, items met by more than six ops run the chain in chunks)
-#ifndef IPPM_TILE_WAVES_PER_EU
 #define IPPM_TILE_WAVES_PER_EU 5
-#endif
 // (the untracked tile-storage instantiation needs 84 registers for its six wavefronts' 80: four are spilled (20 bytes of scratch, re-read around the items).
 //  Measured alternatives, profiles/r06/tile_storage_ab.txt: five wavefronts per SIMD and no spill 149 against 141 us at 2048 envs x 4 UAVs x 256^2, 865 against 873 at config
 //  4's shape; the row packed into the column register: nine spills, 157 us; per-slot row masks built before the chain: twenty-eight.)
-#ifndef IPPM_TL_WAVES_PER_EU
 #define IPPM_TL_WAVES_PER_EU 6
-#endif
 template <bool MIS, bool TRACK, bool TL = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(!MIS && !TRACK ? (TL ? IPPM_TL_WAVES_PER_EU : 6) : (TRACK ? 4 : IPPM_TILE_WAVES_PER_EU), 8)))
 k_fuse_tiles(const int32_t* __restrict__ work, int n_envs, int env_cap, int rot, int n, int gx, int gy, int row_bytes, int TB, float lc, float wt,
@@ -472,10 +442,6 @@ k_fuse_tiles(const int32_t* __restrict__ work, int n_envs, int env_cap, int rot,
   const int count = tag & IPPM_WORK_COUNT;
   if (first >= count) return;
   __shared__ double s_area[TRACK ? IPPM_FEAT * IPPM_AREA_LD + IPPM_AREA_LD : 1];
-#ifdef IPPM_X_LDS_PAD   // measurement-only variants (make VARIANT=occN EXTRA=-DIPPM_X_LDS_PAD=bytes): LDS nobody needs, to cap the wavefronts a CU holds (160 KB / bytes)
-  __shared__ int s_pad[IPPM_X_LDS_PAD / 4];
-  if (n_envs < 0) { s_pad[threadIdx.x] = first; __syncthreads(); if (counters) counters[0] += s_pad[(threadIdx.x + 1) & 63]; }
-#endif
   if (TRACK) {
     for (int k = lane; k < IPPM_FEAT * IPPM_AREA_LD + IPPM_AREA_LD; k += 64) s_area[k] = 0.0;
     __syncthreads();
@@ -503,7 +469,7 @@ k_fuse_tiles(const int32_t* __restrict__ work, int n_envs, int env_cap, int rot,
     else if (na == 2) tile_item<2, 4, MIS, TRACK, TL>(w, acc, env, slot, x0, cnt, gs, g0, W, active);
     else if (na == 3) tile_item<3, 4, MIS, TRACK, TL>(w, acc, env, slot, x0, cnt, gs, g0, W, active);
     else if (na == 4) tile_item<4, 4, MIS, TRACK, TL>(w, acc, env, slot, x0, cnt, gs, g0, W, active);
-    else if (na <= 6) tile_item<6, IPPM_X_SLOTS56, MIS, TRACK, TL>(w, acc, env, slot, x0, cnt, gs, g0, W, active);
+    else if (na <= 6) tile_item<6, 2, MIS, TRACK, TL>(w, acc, env, slot, x0, cnt, gs, g0, W, active);
     else tile_item_long<MIS, TRACK, TL>(w, acc, env, slot, x0, cnt, gs, g0, W, active);
     it = nx;
   }
@@ -542,7 +508,7 @@ int ippm_launch_fuse_tiles(ippm_ctx* ctx, float* local, float* global, const uin
   // than 1024 for everybody -- measured while each env's list still ran on one XCD (see `rot` below), which is what held those
   // launches up, not their longest chains; profiles/r05/c5_wave_distribution.txt)
   const double est_items = 0.5 * (c.n_agents + 1) * (double)c.grid_x * c.grid_y / 3.0 / (256.0 * ippm_tile_slots(max_ops));
-  int per_env = ctx->knob_tile_waves > 0 ? ctx->knob_tile_waves : (int)std::max(4.0, std::min(2048.0, est_items / 3.0));
+  int per_env = (int)std::max(4.0, std::min(2048.0, est_items / 3.0));
   per_env = std::max(1, std::min(per_env, env_cap));
   // a launch smaller than the chip's wave slots leaves CUs idle: small batches take more wavefronts per env
   while ((long long)per_env * n_envs < 16384 && per_env * 2 <= env_cap && per_env < 256) per_env *= 2;

@@ -44,12 +44,7 @@
 #define OP_XR 6
 #define OP_LM1 7
 #define IPPM_MAX_OPS (IPPM_MAX_AGENTS + 2)
-// Variant builds only (make VARIANT=skewN EXTRA=-DIPPM_MAP_SKEW=N; tools/alloc_skew_sample.py): N floats of padding behind every map, honoured
-// by K3's tile form, the tile fusion and k_reset_maps -- the env-only step -- and by nothing else.  0 in the product library.
-#ifndef IPPM_MAP_SKEW
-#define IPPM_MAP_SKEW 0
-#endif
-#define IPPM_MAP_PITCH(gx, gy) ((size_t)(gx) * (size_t)(gy) + IPPM_MAP_SKEW)
+#define IPPM_MAP_PITCH(gx, gy) ((size_t)(gx) * (size_t)(gy))   // floats from one map to the next
 #define IPPM_COUNTER_SLOTS 64  // work counters are spread over 64 slots to keep atomics off one address
 
 // sums layout: double [E, 8]
@@ -66,9 +61,9 @@ struct ippm_ctx {
   ippm_config* dcfg;         // device copy
   unsigned long long* dcounters;  // device, IPPM_COUNTER_SLOTS x 8 words (summed into ippm_counters on read)
   int vec;                   // 4: 16-byte lane groups (grid_y >= 44), else 1
-  // tuning knobs, resolved ONCE at ippm_ctx_create (the work buffer's size, the plan kernel's item layout and the fusion launch
-  // all derive from them and must agree for the context's lifetime)
-  int knob_wave_rows, knob_persist, knob_nowork, knob_split, knob_tile_waves, knob_tile_rotate, knob_plan_builders, knob_k3_dense, knob_terrain_one_launch, knob_reset_align, knob_tile_round, knob_k3_round;
+  // environment knobs, resolved ONCE at ippm_ctx_create (the work buffer's size, the plan kernel's item layout and the fusion launch
+  // all derive from the context's settings and must agree for its lifetime)
+  int knob_tile_rotate, knob_terrain_one_launch;
   int32_t* slabs = nullptr;    // ippm_set_dirty_slabs: per (env, map, 16-row slab) the column interval written since the episode's reset (device, caller-owned)
   const int32_t* n_active;   // device int32 [E] or nullptr: agents flying in each env (ippm_set_team_sizes)
   int k3_wpg, k3_chn, k3_go;        // workgroup shape of the env-only step's K3 (wavefronts per workgroup, loads in flight per lane)
@@ -105,8 +100,6 @@ int ippm_work_env_cap(const ippm_ctx* ctx, int n_envs);    // items an env's sli
 // [E][cap] items of 4 words {run's first group | lane-loads << 16, first row, region's first group | groups per row << 16,
 // op mask | map slot << 24}, cap = ippm_tile_env_cap().
 int ippm_tile_env_cap(const ippm_ctx* ctx);
-// IPPM_TILE_ROUND / IPPM_K3_ROUND: 1 = whole 128-byte lines (32 cells); 8 / 16 / 32 = that many cells (measurement: half and quarter lines)
-static inline int ippm_round_cells(int knob) { return (knob == 8 || knob == 16 || knob == 32) ? knob : 32; }
 static inline int ippm_slab_count(const ippm_ctx* ctx) { return (ctx->cfg.grid_x + IPPM_SLAB_ROWS - 1) / IPPM_SLAB_ROWS; }   // dirty slabs per map
 int ippm_launch_fuse_tiles(ippm_ctx* ctx, float* local, float* global, const uint8_t* code, int32_t* ws, double* sums, double* area,
                            const int32_t* work, int n_envs, hipStream_t st);   // fuse_tiles.hip (area != nullptr: area sums tracked)
@@ -115,10 +108,7 @@ int ippm_launch_fuse_tiles(ippm_ctx* ctx, float* local, float* global, const uin
 #define IPPM_WORK_COUNT 0x0FFFFFFF
 // loads in flight per lane of a tile item, by the number of ops that meet it (the code bytes of every op are in flight too)
 // (4 for up to four ops, 2 beyond: items of more than six ops run their chain six ops at a time, fuse_tiles.hip)
-#ifndef IPPM_X_SLOTS56     // measurement-only variants (make VARIANT=slots4 EXTRA=-DIPPM_X_SLOTS56=4): loads in flight per lane of an item met by five or six ops
-#define IPPM_X_SLOTS56 2
-#endif
-__host__ __device__ inline int ippm_tile_slots(int na) { return na <= 4 ? 4 : (na <= 6 ? IPPM_X_SLOTS56 : 2); }
+__host__ __device__ inline int ippm_tile_slots(int na) { return na <= 4 ? 4 : 2; }
 int ippm_launch_plan(ippm_ctx* ctx, const int32_t* rect, const int32_t* pos, const uint8_t* comm, int32_t* ws, int global_maps,
                      int n_envs, int agent_sel, hipStream_t st);
 // ---- TILE STORAGE of the maps (ippm_ctx::tl, ippm_set_map_layout) ---------------------------------------------------------------------
@@ -240,11 +230,8 @@ struct Philox4 {
 };
 __host__ __device__ __forceinline__ Philox4 ippm_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                                         uint32_t k1) {
-#ifndef IPPM_X_PHILOX_ROUNDS      // measurement-only variants (make VARIANT=ph2 EXTRA=-DIPPM_X_PHILOX_ROUNDS=2): what K3 takes with a cheaper generator
-#define IPPM_X_PHILOX_ROUNDS 10
-#endif
 #pragma unroll
-  for (int r = 0; r < IPPM_X_PHILOX_ROUNDS; ++r) {
+  for (int r = 0; r < 10; ++r) {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
     uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
     uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
@@ -301,12 +288,6 @@ __device__ __forceinline__ void ippm_footprint_rect(const ippm_config* c, int px
   clipped[1] = min(max(yd, 0), gy1);
   clipped[2] = min(max(xl, 0), gx1);
   clipped[3] = min(max(xr, 0), gx1);
-#ifdef IPPM_X_ALIGN_FOOTPRINTS   // measurement-only variant (make VARIANT=alignfp EXTRA=-DIPPM_X_ALIGN_FOOTPRINTS=32): every footprint is
-  {                              // shifted left onto a multiple of that many cells (32 cells = one 128-byte line), same size -- what the
-    const int sh = clipped[0] % IPPM_X_ALIGN_FOOTPRINTS;   // map kernels would take if footprint rows started on line boundaries
-    clipped[0] -= sh; clipped[1] -= sh;
-  }
-#endif
 }
 
 

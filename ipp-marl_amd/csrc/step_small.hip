@@ -245,9 +245,7 @@ __device__ __forceinline__ int tb_lane_i(int v, int lane) { return __builtin_amd
 // every item but a region's last is full whatever the width (round 4 cut regions into blocks of WHOLE rows, floor(cap / W) of
 // them: a 150-group interval filled 150 of 256 lane-loads, and at config 5's shape the list as a whole 77 %).  One LDS atomic
 // reserves the region's slots in the env's list, then lane l writes items l, l + 64, ...
-#ifndef IPPM_TILE_COOP_ITEMS   // regions of more items than this are written by the whole builder wavefront
-#define IPPM_TILE_COOP_ITEMS 6
-#endif
+#define IPPM_TILE_COOP_ITEMS 6   // regions of more items than this are written by the whole builder wavefront
 __device__ __forceinline__ int tile_region_items(int rows, int W, unsigned mask, int& sh) {
   sh = ippm_tile_slots(__popc(mask)) == 4 ? 8 : 7;   // cap = 64 * slots = 1 << sh
   return (rows * W + (1 << sh) - 1) >> sh;
@@ -399,13 +397,6 @@ __global__ void k_action_mask(const ippm_config* __restrict__ c, const int32_t* 
 //                    starts with its rectangle in hand instead of a pos -> lattice index -> centre table chain
 // comm and the plans read the pre-move positions (LDS copy taken before K1 writes anything).
 // ======================================================================================================
-#ifdef IPPM_PLAN_STAMPS   // variant builds: env 0 leaves wall-clock stamps of its phases in word 7 of the counter slots
-#define PLAN_STAMP(k) do { if (blockIdx.x == 0 && lane == 0 && stamps) stamps[((wv * 8 + (k)) & 63) * 8 + 7] = wall_clock64(); \
-    if (blockIdx.x == gridDim.x - 1 && wv == 0 && lane == 0 && stamps) stamps[(48 + (k)) * 8 + 7] = wall_clock64(); \
-    if (blockIdx.x == gridDim.x / 2 && wv == 0 && lane == 0 && stamps) stamps[(56 + (k)) * 8 + 7] = wall_clock64(); } while (0)
-#else
-#define PLAN_STAMP(k) do { } while (0)
-#endif
 #define IPPM_PLAN_BUILDERS 14  // most wavefronts that build tile items next to wavefront 0 (maps are dealt out round-robin); + K1 = 16 wavefronts
 #define IPPM_PLAN_BUILDERS_DEFAULT 3   // measured at 1024 envs x 4 UAVs: 1 / 2 / 3 / 5 builders -> 32.6 / 25.8 / 21.1 / 26.5 us (16 wavefronts
                                        // per CU is what one round of the launch holds; a sixth wavefront per env makes it two rounds)
@@ -416,7 +407,7 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
             const float* __restrict__ probs,
             const int32_t* __restrict__ action_in, uint8_t* __restrict__ mask, int32_t* __restrict__ action,
             int32_t* __restrict__ fault, int32_t* __restrict__ rect_next, int agent_sel, int32_t* __restrict__ work,
-            int wave_rows, int env_cap, unsigned long long* __restrict__ stamps, const int32_t* __restrict__ n_active,
+            int wave_rows, int env_cap, unsigned long long* __restrict__ /* counters: not used here */, const int32_t* __restrict__ n_active,
             int32_t* __restrict__ slabs, int n_slabs, int tile_round) {
   // (argument order = latency order: what the first loads need -- positions, footprints, the maps' clamp state, the team size --
   // arrives in SGPRs with the wavefront, so the loads go out before anything else has been read)
@@ -449,7 +440,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
   const int k1_wave = move ? (tiled && waves >= 3 ? 1 : 0) : -1;   // K1 beside the planning only when builders exist besides it
   int32_t* pg = pos + (size_t)e * n * 3;
   int32_t st[6] = {0, 0, 0, 0, 0, 0};
-  PLAN_STAMP(0);
   if (wv == 0) {
     // everything the workgroup will read is requested now, in one round trip: positions, published footprints, the
     // deferred-clamp state of my map (lane i: local map i, lane n: the global map)
@@ -470,7 +460,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
     if (plans && lane < n * 4) s_rect[lane] = vrect;
   }
   if (waves > 1) __syncthreads(); else wave_sync_lds();
-  PLAN_STAMP(1);
   if (wv == 0 && plans) {
     int hull_rows = 0;
     if (tiled && lane < n) {   // lane j: the op record of agent j's measurement, once for all the maps that will take it
@@ -498,7 +487,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
       wave_sync_lds();
       if (lane < n) recv = s_recv[lane];
     }
-    PLAN_STAMP(7);
     if (tiled) {
       wave_sync_lds();
       if ((flags & IPPM_STEP_COMM) && lane < na && (agent_sel < 0 || agent_sel == lane))
@@ -553,7 +541,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
     }
     if (tiled && lane == 0) __hip_atomic_store(&s_ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);   // the plans are in LDS
   }
-  PLAN_STAMP(2);
   if (tiled && (wv != k1_wave || k1_wave == 0)) {   // (fewer than 3 wavefronts: the planning wavefront builds, then does K1)
     // Tile items: builder b takes maps b, b + nb, ...; an interval's items go wherever the env's running count says (an LDS
     // atomic), so no builder waits for another; the last one to finish writes the env's count.
@@ -561,7 +548,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
     if (wv != 0)
       while (__hip_atomic_load(&s_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
     int4* items = reinterpret_cast<int4*>(work + ((gridDim.x + 3) & ~3)) + (size_t)e * env_cap;
-    PLAN_STAMP(3);
     // Builder 0 is the planning wavefront: it starts last, and it takes the global map, whose plan holds every footprint (about
     // as many items as two or three local plans).  The local maps go to the other builders in turn, every third round of them
     // to builder 0 (4 UAVs, 3 builders: global | locals 0, 2 | locals 1, 3 instead of global + local 2 on the late one: -1 us).
@@ -573,7 +559,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
       const int nops = __builtin_amdgcn_readfirstlane(s_nops[m]);
       if (nops > 0) tile_build_map(s_ops + m * IPPM_MAX_OPS, nops, e, m, items, env_cap, &s_items, lane, tile_round, (c->grid_y + 3) >> 2);
     }
-    PLAN_STAMP(4);
     int last = 0;
     if (lane == 0) last = atomicAdd(&s_done, 1) == nb - 1 ? 1 : 0;
     last = __builtin_amdgcn_readfirstlane(last);
@@ -588,7 +573,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
   if (wv != k1_wave) return;
   // ---- K1 on its own positions; the footprints of the NEW positions for K3, and into the map's sensed-cells box
   wave_sync_lds();
-  PLAN_STAMP(5);
   k1_env(c, episode ? episode[e] : 0, s_pos1, probs ? probs + (size_t)e * n * A : nullptr,
          action_in ? action_in + (size_t)e * n : nullptr, policy, t, mask + (size_t)e * n * A, action + (size_t)e * n,
          fault ? fault + e : nullptr, na);
@@ -610,7 +594,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
     if (ws) box_union(ws + (size_t)(e * (n + 1) + lane) * IPPM_WS_WORDS, cl[2], cl[3], cl[0], cl[1], WS_SBOX_X, WS_SBOX_Y);   // what K3 senses next
     if (slabs) slab_mark(slabs + (size_t)(e * (n + 1) + lane) * 2 * n_slabs, n_slabs, cl[2], cl[3], cl[0], cl[1]);
   }
-  PLAN_STAMP(6);
 }
 
 // ======================================================================================================
@@ -673,11 +656,10 @@ extern "C" int ippm_plan_step(ippm_ctx* ctx, const int64_t* episode, int32_t* po
   if (!ctx || !pos) { ippm_set_error("ippm_plan_step: null argument"); return -1; }
   if ((flags & (IPPM_STEP_COMM | IPPM_STEP_GLOBAL | IPPM_STEP_MOVE)) == 0 || (flags & ~15)) { ippm_set_error("ippm_plan_step: bad flags"); return -1; }
   // The form of the work list follows the CONTEXT, not the caller: ippm_fuse_step hands a list to the tile fusion exactly when
-  // the context has the tile form (and no measurement knob routes it to the row walker), so that is the form built here --
+  // the context has the tile form, so that is the form built here --
   // IPPM_STEP_TILES is implied there and ignored elsewhere.  (Until round 5 the flag decided, and a caller who followed the
   // header -- plan without the flag, fuse with area sums -- got a list the tile fusion skipped: no fusion, rc 0.)
-  const bool tile_ctx = ctx->tiles && !ctx->knob_nowork && !ctx->knob_split;
-  if (tile_ctx && work && (flags & (IPPM_STEP_COMM | IPPM_STEP_GLOBAL))) flags |= IPPM_STEP_TILES;
+  if (ctx->tiles && work && (flags & (IPPM_STEP_COMM | IPPM_STEP_GLOBAL))) flags |= IPPM_STEP_TILES;
   else flags &= ~IPPM_STEP_TILES;
   if ((flags & IPPM_STEP_COMM) && (!comm || !rect || !ws)) { ippm_set_error("ippm_plan_step: comm/plan needs comm, rect, ws"); return -1; }
   if ((flags & IPPM_STEP_COMM) && !draws && !episode) { ippm_set_error("ippm_plan_step: Philox draws need the episode ids"); return -1; }
@@ -703,13 +685,16 @@ extern "C" int ippm_plan_step(ippm_ctx* ctx, const int64_t* episode, int32_t* po
   // per map) take a builder per map as long as the whole launch stays within one round of the chip
   int builders = ctx->cfg.n_agents >= 7 ? 5 : IPPM_PLAN_BUILDERS_DEFAULT;   // (8 UAVs x 1024 envs: 3 / 5 / 7 / 9 builders -> 59.6 / 51.3 / 50.7 / 53.2 us)
   while (builders < std::min(ctx->cfg.n_agents + 1, IPPM_PLAN_BUILDERS) && (long long)n_envs * (builders + 3) <= 4096) ++builders;
-  if (ctx->knob_plan_builders > 0) builders = std::min(ctx->knob_plan_builders, IPPM_PLAN_BUILDERS);
   const int plan_waves = tile_list ? 1 + std::min(ctx->cfg.n_agents + 1, builders) : 1;
+  // the tile fusion's column intervals rounded outwards to whole 128-byte lines (tile_build_map; row-major rows a multiple of 32 cells long):
+  // on for rows of at least 512 cells.  Measured (round 6, profiles/r06/tile_round_ab.txt): 512^2 x 8 UAVs fusion 1045 -> 1024 us and the K3
+  // behind it 286 -> 275; 256^2 x 4 UAVs fusion 74.7 -> 83-87 us (a 90-cell row grows from 3.7 to 4.7 lines' worth of lane-loads there)
+  const bool tile_round = ctx->cfg.grid_y % 32 == 0 && ctx->cfg.grid_y >= 512;
   IPPM_LAUNCH(ctx, IPPM_T_PLAN, k_plan_step, dim3(n_envs), dim3(64 * plan_waves), S_(stream), pos, rect, ws, ctx->cfg.n_agents, flags, t, policy,
                      ctx->dcfg, episode, comm_range, draws, comm, probs, action_in, mask, action, fault, rect_next, -1, plans ? work : nullptr,
                      ippm_fuse_wave_rows(ctx, n_envs), (flags & IPPM_STEP_TILES) ? ippm_tile_env_cap(ctx) : ippm_work_env_cap(ctx, n_envs),
                      ctx->dcounters, ctx->n_active, ctx->slabs, ippm_slab_count(ctx),
-                     ctx->tl ? -1 : ((ctx->cfg.grid_y % 32 == 0 && ctx->knob_tile_round > 0) ? ippm_round_cells(ctx->knob_tile_round) / 4 - 1 : 0));
+                     ctx->tl ? -1 : (tile_round ? 7 : 0));   // tile_build_map's round_mask
   IPPM_LAUNCH_CHECK("plan_step");
   return 0;
 }

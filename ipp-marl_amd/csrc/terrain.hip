@@ -4,9 +4,6 @@
 #include "ippm_internal.h"
 
 #define IPPM_DOMAIN_TERRAIN 3u
-#ifndef IPPM_TERRAIN_ABL   // variant builds: timing ablations (1: no spectrum draw, 2 / 4: no first / second register FFT, 8: no stores)
-#define IPPM_TERRAIN_ABL 0
-#endif
 
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -173,9 +170,7 @@ struct FourStep {
   __device__ __forceinline__ void run(float2 (&v)[N1], float2 (&o)[N2], int q_in, int i2, bool in_active, int q_out, int k1,
                                       bool out_active) {
     if (in_active) {
-#if !(IPPM_TERRAIN_ABL & 2)
       fft_reg<N1>(v);
-#endif
 #pragma unroll
       for (int k = 0; k < N1; ++k) xbuf[q_in * SEQ + k * (N2 + 1) + i2] = cmul(v[k], twn[i2 * k]);
     }
@@ -183,9 +178,7 @@ struct FourStep {
     if (out_active) {
 #pragma unroll
       for (int i = 0; i < N2; ++i) o[i] = xbuf[q_out * SEQ + k1 * (N2 + 1) + i];
-#if !(IPPM_TERRAIN_ABL & 4)
       fft_reg<N2>(o);
-#endif
     }
   }
 };

@@ -1,7 +1,7 @@
 """A/B of library knobs (environment variables read at ippm_ctx_create) or variant libraries on ONE allocation of the hot planes:
 every setting gets its own VecEnv, all of them use the first one's arena (so the allocation lottery of DESIGN section 2 cannot
 decide the comparison), and timed episodes alternate between the settings.
-    python tools/ab_knobs.py [--rounds 4] [--envs 1024 --agents 4 --grid 256] "" "IPPM_NO_HTAB=1" "IPPM_TILE_WAVES=48" ...
+    python tools/ab_knobs.py [--rounds 4] [--envs 1024 --agents 4 --grid 256] "" "IPPM_NO_TILES=1" "IPPM_TILE_ROTATE=0" ...
 A setting is a space-separated list of NAME=VALUE (empty string = defaults).  Prints avg / min us per launch of the step's kernels."""
 import argparse
 import os

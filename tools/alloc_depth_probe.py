@@ -1,5 +1,5 @@
 """Round 5: does the kind of an allocation (fast / slow for the env's map kernels) depend on how much device memory
-is already held?  tools/alloc_skew_sample.py saw, in three processes in a row, the first 9-10 fresh hipMalloc arenas slow and the next
+is already held?  Round 5's map-pitch sweep (profiles/r05/alloc_skew_sample.txt) saw, in three processes in a row, the first 9-10 fresh hipMalloc arenas slow and the next
 ones fast.  Here: a ballast of B GB (one hipMalloc, or chunks) is taken first, then DRAWS arenas; (K3 + fusion) us per step of config 2.
     python tools/alloc_depth_probe.py "0,4,8,12,16,24,48" 4 [chunk_gb]"""
 import ctypes as C

@@ -25,4 +25,4 @@ for rep in range(3):
         env.steps(t, policy=POLICY_EXPLICIT, actions=acts, features=False)
         torch.cuda.synchronize(); plan_s += a.elapsed_time(b) * 1e-3
     dt = time.perf_counter() - t0
-print(f"IG policy ({E} envs x {env.d.n_agents} UAVs x {env.d.grid_x}^2, {env.d.n_actions} actions{', per-candidate K9' if os.environ.get('IPPM_IG_PER_CANDIDATE') else ''}): {dt / T * 1e3:.3f} ms per env step ({E * env.d.n_agents * T / dt / 1e6:.2f} M agent-env steps/s), planner {plan_s / T * 1e6:.0f} us per call")
+print(f"IG policy ({E} envs x {env.d.n_agents} UAVs x {env.d.grid_x}^2, {env.d.n_actions} actions): {dt / T * 1e3:.3f} ms per env step ({E * env.d.n_agents * T / dt / 1e6:.2f} M agent-env steps/s), planner {plan_s / T * 1e6:.0f} us per call")
