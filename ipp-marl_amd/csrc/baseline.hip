@@ -22,10 +22,23 @@ __device__ __forceinline__ void ig_action_offset(int A, int a, int s, int& dx, i
 }
 
 // Expected weighted entropy reduction of one cell with (clipped) belief log-odds l under a measurement of log-odds +-ln
-// (IG_baseline.py:236-268):  p (H(l) - H(l + ln)) w(l + ln) + (1 - p) (H(l) - H(l - ln)) w(l - ln),  w = the posterior itself
-// inside the weight band, 1 / 0 beyond it.  All three entropies and posteriors hang off ONE exponential: with e = exp(-|l|),
-// exp(-|l + s|) = exp(-l) exp(-s) or exp(l) exp(s), and exp(+-l) is e or 1/e; kp / km = exp(+-ln), ec = exp(-clip).
-// 8 transcendentals per cell instead of 15.
+// (IG_baseline.py:236-268):  p (H(l) - H(l1)) w(l1) + (1 - p) (H(l) - H(l0)) w(l0),  w = the posterior itself inside the weight
+// band, 1 / 0 beyond it.  The hypothetical posteriors come from mapping.update_cells, which subtracts logit(prior) (mappings.py:
+// 109-124): l1 = l + (ln - lp), l0 = l - (ln + lp); with the default prior 0.5, lp = 0 and both shifts are ln itself, bit for bit.
+// All three entropies and posteriors hang off ONE exponential: with e = exp(-|l|), exp(-|l + s|) = exp(-l) exp(-s) or exp(l) exp(s),
+// and exp(+-l) is e or 1/e; the shifts' exponentials come in ig_shift, ec = exp(-clip).  8 transcendentals per cell instead of 15.
+struct ig_shift {
+  float s1, s0;            // ln - lp, ln + lp
+  float k1p, k1m;          // exp(+-s1)
+  float k0p, k0m;          // exp(+-s0)
+};
+__device__ __forceinline__ ig_shift ig_make_shift(float ln, float lp) {
+  ig_shift k;
+  k.s1 = ln - lp; k.s0 = ln + lp;
+  k.k1p = __expf(k.s1); k.k1m = __expf(-k.s1);
+  k.k0p = __expf(k.s0); k.k0m = __expf(-k.s0);
+  return k;
+}
 __device__ __forceinline__ float ig_entropy_from_e(float a, float e, float& rd) {  // H of |L| = a, e = exp(-a); rd = 1/(1+e)
   const float d = 1.0f + e;
   rd = __builtin_amdgcn_rcpf(d);
@@ -35,7 +48,7 @@ __device__ __forceinline__ float ig_entropy_from_e(float a, float e, float& rd) 
   const float lg = e < 0.015625f ? e * (1.44269504f + e * (-0.72134752f + e * (0.48089835f - 0.36067376f * e))) : __log2f(d);
   return lg + (a * 1.44269504f) * (e * rd);
 }
-__device__ __forceinline__ float ig_cell(float l, float ln, float kp, float km, float ec, float lc, float wt) {
+__device__ __forceinline__ float ig_cell(float l, const ig_shift& k, float ec, float lc, float wt) {
   const float a = fabsf(l), e = __expf(-a), re = __builtin_amdgcn_rcpf(e);
   const bool pos = l >= 0.f;
   const float en = pos ? e : re, ep = pos ? re : e;   // exp(-l), exp(l)
@@ -44,12 +57,12 @@ __device__ __forceinline__ float ig_cell(float l, float ln, float kp, float km, 
   const float pb = pos ? rd : e * rd;                  // sigmoid(l)
   const float qb = pos ? e * rd : rd;                  // 1 - sigmoid(l), formed directly: `1.f - pb` of a saturated cell (pb = 0.9999)
                                                        // keeps 3 digits, and its branch then carries the whole gain of the cell
-  const float l1 = l + ln, l0 = l - ln;
-  // exp(-|l +- ln|), floored at exp(-clip) like the entropy's clipped argument
-  const float e1 = fmaxf(l1 >= 0.f ? en * km : ep * kp, ec), e0 = fmaxf(l0 >= 0.f ? en * kp : ep * km, ec);
+  const float l1 = l + k.s1, l0 = l - k.s0;
+  // exp(-|l1|), exp(-|l0|), floored at exp(-clip) like the entropy's clipped argument
+  const float e1 = fmaxf(l1 >= 0.f ? en * k.k1m : ep * k.k1p, ec), e0 = fmaxf(l0 >= 0.f ? en * k.k0p : ep * k.k0m, ec);
   float rd1, rd0;
   const float h1 = ig_entropy_from_e(fminf(fabsf(l1), lc), e1, rd1), h0 = ig_entropy_from_e(fminf(fabsf(l0), lc), e0, rd0);
-  // inside the weight band |l +- ln| < clip, so e1 / e0 are the unfloored exponentials there
+  // inside the weight band |l1|, |l0| < clip, so e1 / e0 are the unfloored exponentials there
   const float s1 = l1 >= 0.f ? rd1 : e1 * rd1, s0 = l0 >= 0.f ? rd0 : e0 * rd0;
   const float cw1 = l1 > wt ? 1.f : (l1 < -wt ? 0.f : s1);
   const float cw0 = l0 > wt ? 1.f : (l0 < -wt ? 0.f : s0);
@@ -73,7 +86,8 @@ k_ig_candidates(const ippm_config* __restrict__ c, const float* __restrict__ loc
   const int gx = c->grid_x, gy = c->grid_y;
   const int k = ippm_alt_index(c, p[2] + dz);
   const float ln = c->logit_noise[k];  // ln((1-noise)/noise) from the float64 noise level: update_cells(section, 1-noise)
-  const float kp = __expf(ln), km = __expf(-ln), ec = __expf(-c->logit_clip);
+  const ig_shift ks = ig_make_shift(ln, c->logit_prior);
+  const float ec = __expf(-c->logit_clip);
   const float lc = c->logit_clip, wt = c->logit_weight_thr;
   const float* map = local + (size_t)(e * n + i) * gx * gy;
   const bool vec = gy >= 4;   // 16-byte groups at any row alignment; a row's last group is read cell by cell
@@ -92,9 +106,9 @@ k_ig_candidates(const ippm_config* __restrict__ c, const float* __restrict__ loc
     else v[0] = map[(size_t)x * gy + y];
     for (int q = 0; q < step; ++q) {
       if (y + q < yu || y + q >= yd) continue;
-      // IG_baseline.py:236-268 in log-odds: belief clipped once, hypothetical posteriors L +- ln.  Every cell goes into the
+      // IG_baseline.py:236-268 in log-odds: belief clipped once, hypothetical posteriors L +- ln - logit(prior).  Every cell goes into the
       // float64 sum on its own: a float32 partial over the group showed at 2e-5 on a candidate whose gain nearly cancels
-      acc += (double)ig_cell(ippm_clampl(v[q], lc), ln, kp, km, ec, lc, wt);
+      acc += (double)ig_cell(ippm_clampl(v[q], lc), ks, ec, lc, wt);
     }
   }
   // deterministic block reduction in float64
@@ -145,7 +159,8 @@ k_ig_union(const ippm_config* __restrict__ c, const float* __restrict__ local, c
   }
   const int k = ippm_alt_index(c, p[2] + dz);
   const float ln = c->logit_noise[k];
-  const float kp = __expf(ln), km = __expf(-ln), ec = __expf(-c->logit_clip);
+  const ig_shift ks = ig_make_shift(ln, c->logit_prior);
+  const float ec = __expf(-c->logit_clip);
   const float lc = c->logit_clip, wt = c->logit_weight_thr;
   const float* map = local + (size_t)(e * n + i) * gx * gy;
   double acc[9];
@@ -171,8 +186,8 @@ k_ig_union(const ippm_config* __restrict__ c, const float* __restrict__ local, c
 #pragma unroll
       for (int q = 0; q < 9; ++q) any |= ok[q] && inx[q / 3] && iny[q % 3];
       if (!any) continue;
-      // IG_baseline.py:236-268 in log-odds: belief clipped once, hypothetical posteriors L +- ln
-      const double g = (double)ig_cell(ippm_clampl(v[j], lc), ln, kp, km, ec, lc, wt);
+      // IG_baseline.py:236-268 in log-odds: belief clipped once, hypothetical posteriors L +- ln - logit(prior)
+      const double g = (double)ig_cell(ippm_clampl(v[j], lc), ks, ec, lc, wt);
 #pragma unroll
       for (int q = 0; q < 9; ++q) acc[q] += ok[q] && inx[q / 3] && iny[q % 3] ? g : 0.0;
     }

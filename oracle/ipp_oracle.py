@@ -940,7 +940,11 @@ def f1_target(gmap: np.ndarray, truth: np.ndarray) -> float:
 class OracleIGBaseline:
     """IG_baseline.execute (:56-220) with injected sensing randomness (see OracleEpisode for the conventions)."""
 
-    def __init__(self, params: Dict, episode: int, correctness: Callable, comm_draw: Optional[Callable] = None, exact: bool = False):
+    def __init__(self, params: Dict, episode: int, correctness: Callable, comm_draw: Optional[Callable] = None, exact: bool = False,
+                 actions: Optional[Callable] = None):
+        # actions(i, t): fly these decisions instead of the planner's own (gains and utilities are still evaluated and logged) -- how
+        # an exact-arithmetic run is kept on the trajectory of a recorded one
+        self.actions = actions
         self.d = Derived(params)
         self.d.exact = exact
         self.episode = episode
@@ -992,7 +996,7 @@ class OracleIGBaseline:
             util = ig_cell_utilities(pos_lists, rel) if self.communication else rel
             step_actions, alts, m2cs = [], [], []
             for i in range(n):
-                a = int(np.argmax(util[i]))
+                a = int(np.argmax(util[i])) if self.actions is None else int(self.actions(i, t))
                 agents[i]["position"] = action_to_position(d, agents[i]["position"], a)
                 sense(i)
                 m2cs.append(agents[i]["map2communicate"])

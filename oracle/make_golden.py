@@ -611,10 +611,14 @@ def gen_coma_step():
 
 # ------------------------------------------------------------------ IG baseline (BASELINE config 1)
 def gen_ig_baseline():
+    """The reference's own IG_baseline runs.  The last two anchor the oracle's 27-action and mapping.prior != 0.5 planner paths
+    (three altitude layers; mapping.update_cells' logit(prior) in the hypothetical posteriors)."""
     import marl_framework.IG_baseline as ref_ig
     from marl_framework import constants
     for tag, params, episode in (("ig_c1_e1", make_params("c1"), 1),
-                                 ("ig_small3_e4", make_params("small", experiment__missions__n_agents=3), 4)):
+                                 ("ig_small3_e4", make_params("small", experiment__missions__n_agents=3), 4),
+                                 ("ig_small3_a27_e5", make_params("small", experiment__missions__n_agents=3, experiment__constraints__num_actions=27), 5),
+                                 ("ig_small3_prior03_e6", make_params("small", experiment__missions__n_agents=3, mapping__prior=0.3), 6)):
         torch.manual_seed(99 + episode)
         np.random.seed(77 + episode)
         with Recorder() as rec:

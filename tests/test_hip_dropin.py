@@ -177,7 +177,7 @@ def test_batch_memory_td_targets(golden):
     assert len(batches) == (n * L) // 60 and all(len(b) == 60 for b in batches)
 
 
-@pytest.mark.parametrize("tag", ["ig_c1_e1", "ig_small3_e4"])
+@pytest.mark.parametrize("tag", ["ig_c1_e1", "ig_small3_e4", "ig_small3_a27_e5", "ig_small3_prior03_e6"])
 def test_ig_baseline_replays_reference_run(golden, tag, monkeypatch):
     """IG_baseline(params, writer, episode).execute() as IG_baseline.main drives it (BASELINE config 1 and a smaller case),
     with the sensor noise the reference drew: chosen altitudes, candidate gains, target entropy and F1 per step."""
@@ -193,15 +193,26 @@ def test_ig_baseline_replays_reference_run(golden, tag, monkeypatch):
     ig = IG_baseline(params, None, int(fx["episode"]))
     ig.replay = ReplayHooks(correctness=lambda agent_id, stage: corr[stage * n + agent_id])
     rel, ab, altitudes, entropies, f1s = ig.execute()
+    # (The planner flies its OWN decisions here.  In the prior-0.3 recording one of them is a near-tie: the oracle's exact float64 run, left
+    #  to its argmax, leaves the recorded trajectory at step 14, while the device's float32 rounding falls the recorded way.  That is
+    #  deterministic, but a legitimate change of K9's rounding may move it: a failure of THIS assertion for that tag alone, with the gains
+    #  of the steps before it still within tolerance, is that near-tie and not a wrong gain.)
     assert np.array_equal(np.array(altitudes), fx["altitudes"])
-    np.testing.assert_allclose(np.array(ig.gains_log), fx["gains"], rtol=RTOL, atol=1e-9)
+    from test_oracle_golden import oracle_ig_run
+    if params["mapping"]["prior"] == 0.5:
+        np.testing.assert_allclose(np.array(ig.gains_log), fx["gains"], rtol=RTOL, atol=1e-9)
+    else:
+        # With another prior every fusion shifts every cell, the maps drift to the clip, and the RECORDED gains carry the reference's own
+        # float32 re-quantisation noise there (up to 6.1e-4 relative in this recording: test_oracle_golden.py::
+        # test_ig_recording_at_prior03_carries_reference_quantisation, measured on the CPU between the oracle's two modes).  The device keeps
+        # log-odds and has no such noise: it is held, at the same tolerance, to the oracle's exact-arithmetic run of the recorded trajectory.
+        np.testing.assert_allclose(np.array(ig.gains_log), np.array(oracle_ig_run(fx, tag, exact=True)[0]["gains"]), rtol=RTOL, atol=1e-9)
     np.testing.assert_allclose(entropies, fx["entropies"], rtol=RTOL)
     # F1 thresholds the map at p > 0.5.  Cells whose observations cancel exactly (47 % of the twice-observed cells at 15 m)
     # sit at 0.5 +- 1e-8 in the reference and are classified by its rounding noise, so the recorded F1 can only be
     # bracketed: every such cell in the wrong class <= reference <= every such cell in the right class.
     assert f1s[0] == fx["f1"][0] == 0.0
     _check_f1_brackets(ig, fx)
-    from test_oracle_golden import oracle_ig_run
     _check_f1_counts(ig, oracle_ig_run(fx, tag)[1])
     np.testing.assert_allclose([rel, ab], [fx["relative_return"], fx["absolute_return"]], rtol=1e-9)
 
@@ -308,22 +319,29 @@ def test_coma_test_replays_reference_run(golden):
 
 
 def test_batched_ig_policy_matches_oracle(name="small", over=None, seed=5, first_episode=40, n_envs=6):
-    """VecEnv.ig_actions (K9 + K10 for all envs at once) against the oracle's literal restatement.
+    """VecEnv.ig_actions (K9 + K10 for all envs at once) against the oracle's literal restatement, over the whole budget.
     (The arguments: tools/stress_parity.py sweeps random configurations through this same check.)"""
+    check_batched_ig_policy(name, over, seed, first_episode, n_envs)
+
+
+def check_batched_ig_policy(name, over, seed, first_episode, n_envs, communication=True, map_layout="auto", steps=None):
+    """Every step: the device's gains against O.ig_individual on the device's own maps, its decisions against np.argmax of the oracle's
+    utilities.  Returns (decisions, decisions excused as proven ties)."""
     from ippmarl.vec_env import VecEnv, POLICY_EXPLICIT
     params = make_params(name, **(over or {}))
     d = O.Derived(params)
     d.exact = True
-    env = VecEnv(params, n_envs, philox_seed=seed)
+    env = VecEnv(params, n_envs, philox_seed=seed, map_layout=map_layout)
     eps = np.arange(first_episode, first_episode + n_envs)
     env.reset(eps)
-    for t in range(4):
+    decisions = excused = 0
+    for t in range(d.budget + 1 if steps is None else steps):
         env.build_observations(t, features=False)
         # the beliefs the planner sees, as float64 probabilities of the stored log-odds (a float32 probability of a saturated cell,
         # 0.9999, keeps three digits of 1 - p, and a candidate over nothing but saturated cells has a gain made of exactly that)
         local = 1.0 / (1.0 + np.exp(-env.rows_view(env.local).cpu().numpy().astype(np.float64)))
         pos = env.pos.cpu().numpy()
-        acts = env.ig_actions(communication=True)
+        acts = env.ig_actions(communication=communication)
         gains, chosen = env.ig_gains.cpu().numpy(), acts.cpu().numpy()
         for e in range(env.E):
             pls, gls, prior = [], [], []
@@ -332,16 +350,52 @@ def test_batched_ig_policy_matches_oracle(name="small", over=None, seed=5, first
                 ap, g = O.ig_individual(d, pos[e, i], m, local[e, i])
                 np.testing.assert_allclose(gains[e, i], g, rtol=RTOL, atol=1e-9)
                 pls.append(ap), gls.append(g), prior.append(pos[e, i])
-            util = O.ig_cell_utilities(pls, O.ig_relative(gls))
+            rel = O.ig_relative(gls)
+            util = O.ig_cell_utilities(pls, rel) if communication else rel
             for i, u in enumerate(util):
                 want, got = int(np.argmax(u)), int(chosen[e][i])
+                decisions += 1
                 if want != got:
                     # Agents in contact hold identical fused maps, hence identical gains; two of them eyeing the same two cells
                     # crosswise get utilities p (1 - q) and (1 - p)(1 - (1 - q)) with q = p -- equal in exact arithmetic, told
                     # apart only by the rounding of 1 - (1 - p) (float64 in the reference, float32 here).  Only such ties may differ.
                     u = np.asarray(u, dtype=np.float64)
                     assert abs(u[want] - u[got]) <= 1e-6 * abs(u[want]), (t, e, i, u.tolist(), want, got)
+                    excused += 1
         env.steps(t, policy=POLICY_EXPLICIT, actions=acts, features=False)
+    # exact ties are real here (identical maps after fusion), but they are rare: a case that needs the rule for more than one decision
+    # in twenty is not deciding by the oracle's numbers any more
+    assert excused <= 0.05 * decisions, (excused, decisions)
+    return decisions, excused
+
+
+IG_POLICY_CASES = {
+    # name: (config, overrides, envs, communication, map layout)
+    "a27": ("small", {"experiment__constraints__num_actions": 27}, 4, True, "auto"),
+    "a9_planar": ("small", {"experiment__constraints__num_actions": 9, "experiment__constraints__min_altitude": 15,
+                            "experiment__constraints__max_altitude": 15}, 4, True, "auto"),
+    "a4": ("small", {"experiment__constraints__num_actions": 4, "experiment__constraints__min_altitude": 15,
+                     "experiment__constraints__max_altitude": 15}, 4, True, "auto"),
+    "a6_no_communication": ("small", {}, 4, False, "auto"),
+    "a27_rect_128x256": ("small", {"experiment__constraints__num_actions": 27, "environment__x_dim": 50, "environment__y_dim": 100}, 3, True, "auto"),
+    "a27_tiles": ("small", {"experiment__constraints__num_actions": 27}, 4, True, "tiles"),
+    "a6_tiles": ("small", {}, 4, True, "tiles"),
+    "a27_6uavs_link_failures": ("small", {"experiment__constraints__num_actions": 27, "experiment__missions__n_agents": 6,
+                                          "experiment__uav__failure_rate": 0.3, "experiment__uav__communication_range": 15}, 3, True, "auto"),
+    "c5_3uavs": ("c5", {"experiment__missions__n_agents": 3}, 2, True, "auto"),
+    "a6_prior03": ("small", {"mapping__prior": 0.3}, 4, True, "auto"),
+    "a27_prior03": ("small", {"mapping__prior": 0.3, "experiment__constraints__num_actions": 27}, 4, True, "auto"),
+}
+
+
+@pytest.mark.parametrize("case", list(IG_POLICY_CASES))
+def test_batched_ig_policy_cases(case):
+    """The check above over the action sets (27: k_ig_union's three layers; 9: one layer; 4: the planar table of the per-candidate
+    kernel), without communication, on a rectangular world, in tile storage, with six UAVs and failing links, on the 1024 x 1024 grid
+    and with mapping.prior = 0.3 (hypothetical posteriors l +- ln - logit(prior)), every step of the budget."""
+    name, over, n_envs, communication, layout = IG_POLICY_CASES[case]
+    decisions, excused = check_batched_ig_policy(name, over, seed=7, first_episode=23, n_envs=n_envs, communication=communication, map_layout=layout)
+    print(f"{case}: {excused} of {decisions} decisions excused as proven ties")
 
 
 def test_state_and_metric_helpers_match_reference(golden):

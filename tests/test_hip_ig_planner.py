@@ -1,0 +1,614 @@
+"""GPU tests of the greedy information-gain planner's kernels (csrc/baseline.hip: K9 ippm_ig_candidates = k_ig_candidates for the 4- and
+6-action sets, k_ig_union for the 9- and 27-action sets; K10 ippm_ig_select) on inputs BUILT to reach every path, against the
+oracle's literal restatement of the reference (ig_individual / ig_relative / ig_cell_utilities) in float64.
+
+No expected number comes from the kernels: gains and decisions come from the oracle, determinism from bit-equality of two device runs.
+Ties are a condition of the inputs, not a tolerance: every agent owns a distinct map, the oracle's relative gap between an agent's best
+and second-best utility is asserted >= MIN_GAP on the CPU before the device is touched (next seed otherwise, at most RESEEDS times), and
+every decision must then equal np.argmax of the oracle's utilities."""
+import warnings
+
+import numpy as np
+import pytest
+
+import ipp_oracle as O
+from configs import make_params
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+RTOL, ATOL = 1e-5, 1e-9      # the project's tolerance for gains (test_hip_dropin.py::test_batched_ig_policy_matches_oracle)
+MIN_GAP = 1e-4               # ten times the 1e-5 the gains are held to: a gain at the edge of its tolerance cannot turn a decision
+RESEEDS = 3
+
+A27 = dict(experiment__constraints__num_actions=27)
+FLOOR15 = dict(experiment__constraints__min_altitude=15, experiment__constraints__max_altitude=15)
+A9 = dict(experiment__constraints__num_actions=9, **FLOOR15)      # the planar sets are self-consistent with one altitude level only
+A4 = dict(experiment__constraints__num_actions=4, **FLOOR15)
+
+
+# ---- the device side: a bare context and caller-owned tensors, as IG_baseline.get_individual_ig calls the entry points ----------------
+
+class Planner:
+    def __init__(self, params, tiled=False):
+        from ippmarl import _ffi
+        from ippmarl.derived import DerivedConstants
+        assert torch.cuda.is_available()
+        self.ffi, self.dc = _ffi, DerivedConstants(params)
+        self.ctx = _ffi.Context(self.dc)
+        self.ctx.call("ippm_set_map_layout", 1 if tiled else 0)
+        self.tiled = tiled
+        self.dev = torch.device("cuda:0")
+
+    @property
+    def stream(self):
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def upload_maps(self, logodds):
+        """Row-major float32 log-odds [E, N, gx, gy] -> the context's storage (tile storage through ippm_maps_relayout: the test owns the
+        row-major truth the oracle sees)."""
+        rows = torch.from_numpy(np.ascontiguousarray(logodds)).to(self.dev)
+        if not self.tiled:
+            return rows
+        stored = torch.empty_like(rows)
+        self.ctx.call("ippm_maps_relayout", self.ffi.ptr(rows), self.ffi.ptr(stored), rows.shape[0] * rows.shape[1], 1, self.stream)
+        return stored
+
+    def _check_shapes(self, pos, mask, maps=None):
+        """The entry points take bare pointers and stride them by the CONTEXT's team size, action count and grid: a tensor of another
+        shape would be read and written out of bounds."""
+        E, N, A = mask.shape
+        assert (N, A) == (self.dc.n_agents, self.dc.n_actions) and tuple(pos.shape) == (E, N, 3), (mask.shape, pos.shape)
+        assert maps is None or tuple(maps.shape) == (E, N, self.dc.grid_x, self.dc.grid_y), maps.shape
+        return E, N, A
+
+    def candidates(self, maps, pos, mask):
+        E, N, A = self._check_shapes(pos, mask, maps)
+        gains = torch.full((E, N, A), float("nan"), dtype=torch.float32, device=self.dev)   # every entry must be written
+        self.ctx.call("ippm_ig_candidates", self.ffi.ptr(maps), self.ffi.ptr(pos), self.ffi.ptr(mask), self.ffi.ptr(gains), E, self.stream)
+        return gains
+
+    def select(self, pos, mask, gains, communication):
+        E, N, A = self._check_shapes(pos, mask)
+        assert gains.shape == mask.shape and gains.dtype == torch.float32
+        action = torch.full((E, N), -1, dtype=torch.int32, device=self.dev)
+        util = torch.full((E, N, A), -7.0, dtype=torch.float32, device=self.dev)
+        self.ctx.call("ippm_ig_select", self.ffi.ptr(pos), self.ffi.ptr(mask), self.ffi.ptr(gains), 1 if communication else 0,
+                      self.ffi.ptr(action), self.ffi.ptr(util), E, self.stream)
+        return action.cpu().numpy(), util.cpu().numpy()
+
+    def dev_i32(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.dev)
+
+    def dev_u8(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(self.dev)
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+# ---- the oracle side ---------------------------------------------------------------------------------------------------------------
+
+def sigmoid64(logodds):
+    """Float64 probabilities of the very float32 log-odds uploaded (-inf -> 0, +inf -> 1; the oracle clips them like any other cell)."""
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-logodds.astype(np.float64)))
+
+
+def oracle_gains(d, logodds, pos, mask):
+    """O.ig_individual for every (env, agent): gains float64 [E, N, A] and the candidate position lists."""
+    E, N, A = mask.shape
+    prob = sigmoid64(logodds)
+    gains, plists = np.zeros((E, N, A)), []
+    for e in range(E):
+        row = []
+        for i in range(N):
+            ap, g = O.ig_individual(d, pos[e, i], mask[e, i], prob[e, i])
+            gains[e, i] = np.array(g, dtype=np.float64)
+            row.append(ap)
+        plists.append(row)
+    return gains, plists
+
+
+def oracle_utilities(plists_env, gains_env, communication=True):
+    """get_relative_ig (+ get_cell_utilities) of one env on float64 gains: (utilities [N, A], undiscounted relative gains [N, A])."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        rel = O.ig_relative([[np.float64(v) for v in row] for row in gains_env])
+        plain = np.array(rel, dtype=np.float64)
+        util = O.ig_cell_utilities(plists_env, rel) if communication else rel
+    return np.array(util, dtype=np.float64), plain
+
+
+def min_decision_gap(util, skip=()):
+    """Smallest relative gap between the best and the second-best utility over the rows that hold no nan (a row with a nan is decided
+    by np.argmax's rule -- the first nan --, not by a comparison of numbers).  ``skip``: rows that are ties by construction."""
+    gap = np.inf
+    for r, u in enumerate(util.reshape(-1, util.shape[-1])):
+        if r in skip or np.isnan(u).any():
+            continue
+        s = np.sort(u)[::-1]
+        if s[0] > 0:
+            gap = min(gap, (s[0] - s[1]) / s[0])
+    return gap
+
+
+# ---- constructed K9 inputs ---------------------------------------------------------------------------------------------------------
+
+def altitude_levels(d):
+    return [d.min_altitude + k * d.spacing for k in range(d.space_z)]
+
+
+def extreme_points(d):
+    """World corners and edge midpoints at the lowest and the highest altitude: footprints clipped on each side, candidates that leave
+    the lattice (and are masked for it)."""
+    X, Y = (d.space_x - 1) * d.spacing, (d.space_y - 1) * d.spacing
+    mx, my = (d.space_x // 2) * d.spacing, (d.space_y // 2) * d.spacing
+    zs = altitude_levels(d)
+    pts = []
+    for k, (x, y) in enumerate([(0, 0), (X, Y), (0, Y), (X, 0), (mx, 0), (X, my), (mx, Y), (0, my)]):
+        pts.append((x, y, zs[0] if k % 2 == 0 else zs[-1]))
+    for k, (x, y) in enumerate([(0, 0), (X, Y), (0, Y), (X, 0), (mx, 0), (X, my), (mx, Y), (0, my)]):
+        pts.append((x, y, zs[-1] if k % 2 == 0 else zs[0]))
+    out = []
+    for p in pts:
+        if p not in out:
+            out.append(p)
+    return out
+
+
+def build_positions(d, E, rng):
+    """int32 [E, N, 3]: envs 0 .. 2 stand on the extremes, the others on random lattice points; no two agents of an env share one."""
+    N, zs = d.n_agents, altitude_levels(d)
+    pos = np.zeros((E, N, 3), dtype=np.int32)
+    ext = extreme_points(d)
+    for e in range(E):
+        taken = []
+        for i in range(N):
+            k = e * N + i
+            if e < 3 and ext[k % len(ext)] not in taken:
+                p = ext[k % len(ext)]
+            else:
+                while True:
+                    p = (int(rng.randint(d.space_x)) * d.spacing, int(rng.randint(d.space_y)) * d.spacing, zs[int(rng.randint(len(zs)))])
+                    if p not in taken:
+                        break
+            taken.append(p)
+            pos[e, i] = p
+    return pos
+
+
+def build_masks(d, pos, rng):
+    """uint8 [E, N, A]: the legal mask (boundary + collision against the agents before, as the planner is driven) in envs 0, 1 and 3;
+    random SUBSETS of it elsewhere -- per block of nine candidates (a layer of the union walk) 0 .. all of the legal ones stay live;
+    the last agent of the last env keeps none, and the first agent of env 4 loses its first layer."""
+    E, N, _ = pos.shape
+    A = d.num_actions
+    mask = np.zeros((E, N, A), dtype=np.uint8)
+    for e in range(E):
+        before = []
+        for i in range(N):
+            m = O.apply_collision_mask(d, pos[e, i], O.action_mask(d, pos[e, i]), before)
+            before.append(pos[e, i])
+            m = (np.asarray(m) != 0).astype(np.uint8)
+            if e not in (0, 1, 3):
+                block = 9 if A in (9, 27) else A
+                for b0 in range(0, A, block):
+                    live = np.flatnonzero(m[b0:b0 + block]) + b0
+                    keep = rng.choice(live, size=int(rng.randint(0, len(live) + 1)), replace=False) if len(live) else []
+                    m[b0:b0 + block] = 0
+                    m[np.asarray(keep, dtype=np.int64)] = 1
+            mask[e, i] = m
+    if E > 4:
+        mask[4, 0, :min(9, A)] = 0
+    mask[E - 1, N - 1] = 0
+    return mask
+
+
+def build_maps(d, lc, E, rng):
+    """float32 log-odds [E, N, gx, gy], every agent its own: the prior, with blobs of observed cells (p in 0.02 .. 0.98, cell by
+    cell), saturated cells (+-clip exactly), cells BEYOND the clip (the deferred clamp leaves such cells in the local maps) and at
+    +-inf; map (0, 0) is saturated everywhere (a candidate over nothing but saturated cells: its gain is made of differences of
+    entropies that nearly cancel, DESIGN.md "What the random sweeps found": such gains are 1e-9 .. 1e-7 in size and held by the
+    tolerance's absolute 1e-9 alone)."""
+    N, gx, gy = d.n_agents, int(d.gx), int(d.gy)
+    lc = np.float32(lc)
+    maps = np.full((E, N, gx, gy), np.float32(np.log(d.prior / (1 - d.prior))), dtype=np.float32)
+
+    def rect(frac):
+        h, w = max(1, int(rng.randint(gx // 8, max(gx // 8 + 1, int(gx * frac))))), max(1, int(rng.randint(gy // 8, max(gy // 8 + 1, int(gy * frac)))))
+        x0, y0 = int(rng.randint(0, gx - h + 1)), int(rng.randint(0, gy - w + 1))
+        return slice(x0, x0 + h), slice(y0, y0 + w)
+
+    for e in range(E):
+        for i in range(N):
+            m = maps[e, i]
+            for _ in range(4):                                # observed blobs: solid ones ...
+                sx, sy = rect(0.5)
+                p = rng.uniform(0.02, 0.98, size=m[sx, sy].shape)
+                m[sx, sy] = np.log(p / (1 - p)).astype(np.float32)
+            seen = rng.random_sample((gx, gy)) < 0.3          # ... and scattered cells, so that no two footprints hold the same multiset
+            p = rng.uniform(0.02, 0.98, size=int(seen.sum()))
+            m[seen] = np.log(p / (1 - p)).astype(np.float32)
+            for sign in (1, -1):                              # saturated, exactly at the clip
+                sx, sy = rect(0.3)
+                m[sx, sy] = sign * lc
+            for v in (12.5, -12.5, 20.0, -30.0):              # beyond the clip
+                sx, sy = rect(0.15)
+                m[sx, sy] = np.float32(v)
+            for v in (np.inf, -np.inf):
+                xs, ys = rng.randint(0, gx, size=24), rng.randint(0, gy, size=24)
+                m[xs, ys] = np.float32(v)
+    sat = np.where(rng.random_sample((gx, gy)) < 0.5, lc, -lc).astype(np.float32)
+    sat[rng.random_sample((gx, gy)) < 0.02] = np.float32(np.inf)
+    maps[0, 0] = sat
+    return maps
+
+
+def constructed_case(params, E, seed):
+    """Inputs of one K9 / K10 case and the oracle's answer to them; reseeded until the decision gap holds."""
+    from ippmarl.derived import DerivedConstants
+    d = O.Derived(params)
+    d.exact = True
+    lc = DerivedConstants(params).logit_clip
+    for attempt in range(RESEEDS + 1):
+        rng = np.random.RandomState(seed + attempt)
+        pos = build_positions(d, E, rng)
+        mask = build_masks(d, pos, rng)
+        maps = build_maps(d, lc, E, rng)
+        want, plists = oracle_gains(d, maps, pos, mask)
+        utils = np.array([oracle_utilities(plists[e], want[e])[0] for e in range(E)])
+        gap = min_decision_gap(utils)
+        if gap >= MIN_GAP:
+            break
+    assert gap >= MIN_GAP, f"the oracle's decisions on the constructed inputs are closer than {MIN_GAP} ({gap:.3e}) for seeds {seed} .. {seed + RESEEDS}"
+    return d, maps, pos, mask, want, utils
+
+
+K9_CASES = {
+    # name: (config, overrides, envs, tile storage)                                               what it reaches
+    "small_a27": ("small", A27, 6, False),                                                      # k_ig_union, three layers
+    "small_a9_floor15": ("small", A9, 6, False),                                                # k_ig_union, one layer, 42 x 42: row width % 4 = 2
+    "odd51_a27": ("default", dict(sensor__pixel__number_x=6, sensor__pixel__number_y=6, **A27), 6, False),   # 51 x 51, three layers
+    "small_a4": ("small", A4, 6, False),                                                        # k_ig_candidates, the planar table
+    "default_a6": ("default", dict(), 5, False),                                                # k_ig_candidates, 493 x 493: width % 4 = 1
+    "rect_128x256_a27": ("small", dict(environment__x_dim=50, environment__y_dim=100, **A27), 6, False),     # gx != gy in the hull bounds
+    "rect_256x128_a27": ("small", dict(environment__x_dim=100, environment__y_dim=50, **A27), 6, False),
+    "c5_3uav_a27": ("c5", dict(experiment__missions__n_agents=3), 5, False),                    # 1024 x 1024: the largest footprints
+    "small_a27_tiles": ("small", A27, 6, True),                                                 # ippm_cell_index(.., tl), k_ig_union
+    "c2_a9_tiles": ("c2", dict(experiment__constraints__num_actions=9), 6, True),               # 256 x 256, planar moves at all three altitudes
+    "small_a6_tiles": ("small", dict(), 6, True),                                               # ippm_cell_index(.., tl), k_ig_candidates
+    "small_a6_prior03": ("small", dict(mapping__prior=0.3), 6, False),                          # hypothetical posteriors l +- ln - logit(prior)
+    "small_a27_prior03": ("small", dict(mapping__prior=0.3, **A27), 6, False),
+}
+
+
+def k9_device_gains(case):
+    """(params, oracle side of the case, device gains of two runs, the device inputs)."""
+    name, over, E, tiled = K9_CASES[case]
+    params = make_params(name, **over)
+    built = constructed_case(params, E, seed=11)
+    pl = Planner(params, tiled)
+    dmaps, dpos, dmask = pl.upload_maps(built[1]), pl.dev_i32(built[2]), pl.dev_u8(built[3])
+    return params, built, pl, (dmaps, dpos, dmask), pl.candidates(dmaps, dpos, dmask), pl.candidates(dmaps, dpos, dmask)
+
+
+PRIOR05_BITS = "ig_k9_prior05_bits"   # tests/golden: uint32 bit patterns of the gains of eight of the prior-0.5 cases above (a fresh dump holds all), from an MI355X and
+                                      # the build BEFORE K9 read logit_prior, by dump_prior05_bits with IPPMARL_LIB naming that build
+
+
+def dump_prior05_bits(path):
+    """Writes the fixture above from the library in use (with tests/, oracle/ and ipp-marl_amd/ on sys.path)."""
+    out = {case: k9_device_gains(case)[4].cpu().numpy().view(np.uint32).reshape(-1)
+           for case, (name, over, _, _) in K9_CASES.items() if make_params(name, **over)["mapping"]["prior"] == 0.5}
+    np.savez_compressed(path, **out)
+    return {k: len(v) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("case", list(K9_CASES))
+def test_k9_constructed_inputs_match_oracle(case, golden):
+    """ippm_ig_candidates on constructed maps, positions and masks: every gain against O.ig_individual in float64 at the project's
+    tolerance, a masked candidate exactly 0.0, the same call twice bit-identical; then K10 on the device's own gains: every decision
+    equals np.argmax of the oracle's utilities (no tie may be excused: the inputs keep the oracle's gap >= MIN_GAP)."""
+    params, (d, maps, pos, mask, want, utils), pl, (dmaps, dpos, dmask), g1, g2 = k9_device_gains(case)
+    dims = (int(d.gx), int(d.gy))
+    if case == "small_a9_floor15":
+        assert dims == (42, 42)
+    if case == "odd51_a27":
+        assert dims == (51, 51)
+    if case.startswith("rect_128x256"):
+        assert dims == (128, 256)
+    assert torch.equal(bits(g1), bits(g2)), "two runs of K9 on the same inputs differ"
+    got = g1.cpu().numpy()
+    assert np.all(np.isfinite(got))
+    assert np.all(got[mask == 0] == 0.0) and not np.any(np.signbit(got[mask == 0])), "a masked candidate must come back exactly 0.0"
+    live = mask != 0
+    err = np.abs(got.astype(np.float64) - want) / (ATOL + RTOL * np.abs(want))
+    worst = np.unravel_index(int(np.argmax(np.where(live, err, 0))), err.shape)
+    print(f"{case}: {int(live.sum())} live candidates, worst |got - want| / (atol + rtol |want|) = {err[worst]:.3f} at (env, agent, action) {worst}: "
+          f"{got[worst]!r} vs {want[worst]!r}")
+    np.testing.assert_allclose(got, want, rtol=RTOL, atol=ATOL)
+    if params["mapping"]["prior"] == 0.5:
+        # honouring the prior must not move a default-prior result by a bit: logit(0.5) = 0, and l + (ln - 0), l - (ln + 0) are the
+        # expressions K9 had before.  Held to the bits the build before that change produced on these very inputs.
+        recorded = golden(PRIOR05_BITS)
+        if case in recorded:
+            assert np.array_equal(got.view(np.uint32).reshape(-1), recorded[case]), "prior-0.5 gains differ in their bits from the recorded build's"
+    action, _ = pl.select(dpos, dmask, g1, communication=True)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        chosen = np.argmax(utils, axis=-1)
+    assert np.array_equal(action, chosen), (case, np.argwhere(action != chosen).tolist())
+
+
+def test_k9_identical_cell_multisets_give_identical_bits():
+    """The per-candidate kernel promises bit-identical gains for candidates over identical cell multisets (baseline.hip's header): on a
+    map that is constant along x, the footprints of x - s and x + s hold the same cells; on one constant along y, those of y - s and
+    y + s (which start at different 16-byte alignments, so other lanes hold other cells).  Cell gains of p in 0.1 .. 0.9 are float32
+    values above 2^-14: a float64 sum of fewer than 2^16 of them is exact, whatever its order."""
+    params = make_params("default", experiment__missions__n_agents=2)     # 493 x 493, 6 actions: k_ig_candidates
+    d = O.Derived(params)
+    rng = np.random.RandomState(3)
+    gx, gy = int(d.gx), int(d.gy)
+    p_y, p_x = rng.uniform(0.1, 0.9, size=gy), rng.uniform(0.1, 0.9, size=gx)
+    maps = np.zeros((1, 2, gx, gy), dtype=np.float32)
+    maps[0, 0] = np.log(p_y / (1 - p_y)).astype(np.float32)[None, :]
+    maps[0, 1] = np.log(p_x / (1 - p_x)).astype(np.float32)[:, None]
+    pos = np.array([[[25, 25, 10], [25, 30, 10]]], dtype=np.int32)           # mid-world, footprints of every candidate unclipped
+    for p in pos[0]:
+        for a in (1, 2, 3, 4):
+            full, clipped = O.project_field_of_view(d, O.action_to_position(d, p, a))
+            assert full == clipped
+    mask = np.ones((1, 2, 6), dtype=np.uint8)
+    pl = Planner(params)
+    got = pl.candidates(pl.upload_maps(maps), pl.dev_i32(pos), pl.dev_u8(mask))
+    b = bits(got).cpu().numpy()
+    assert b[0, 0, 1] == b[0, 0, 4] and b[0, 0, 1] != b[0, 0, 2]             # x -+ s over a map constant along x
+    assert b[0, 1, 2] == b[0, 1, 3] and b[0, 1, 2] != b[0, 1, 1]             # y -+ s over a map constant along y
+    want, _ = oracle_gains(d, maps, pos, mask)
+    np.testing.assert_allclose(got.cpu().numpy(), want, rtol=RTOL, atol=ATOL)
+
+
+# ---- K10 on hand-built inputs ------------------------------------------------------------------------------------------------------
+
+def k10_oracle(d, pos, mask, gains32, communication):
+    """get_relative_ig + get_cell_utilities on the float32 gains taken as float64: utilities and undiscounted relative gains [E, N, A]."""
+    E, N, A = mask.shape
+    util, plain = np.zeros((E, N, A)), np.zeros((E, N, A))
+    for e in range(E):
+        pls = [[O.action_to_position(d, pos[e, i], a) if mask[e, i, a] else 0 for a in range(A)] for i in range(N)]
+        util[e], plain[e] = oracle_utilities(pls, gains32[e].astype(np.float64), communication)
+    return util, plain
+
+
+def k10_check(pl, d, pos, mask, gains32, communication, tie_rows=()):
+    """Runs K10 and holds it to the oracle.
+
+    Utilities: nan in the same places; elsewhere |got - want| <= (A + 4) 2^-24 (|want| + 2 g1), g1 the entry's undiscounted relative gain.
+    Derivation (first order, rounding unit 2^-24): the kernel sums a row's A non-negative gains in float32 in order (A - 1 roundings)
+    and divides (1 more), so a relative gain is within (A + 1) 2^-24 RELATIVE of the float64 one -- an undiscounted entry is that.  A
+    discounted entry is g1 (1 - rel2): rel2 <= 1, so its error enters 1 - rel2 ABSOLUTELY with at most (A + 1) 2^-24, the subtraction
+    and the product add a rounding each: |got - want| <= (A + 2) 2^-24 |want| + (A + 2) 2^-24 g1.  Where rel2 is an entry of a row
+    before i it is itself discounted and carries up to twice that, 2 (A + 2) 2^-24 g1', with g1' <= 1 its own undiscounted gain, and
+    2 (A + 2) < 2 (A + 4): the bound stated covers both cases.
+    Decisions: np.argmax of the oracle's utilities, exactly (the callers keep the oracle's gap >= MIN_GAP outside ``tie_rows``, whose
+    maxima are bit-equal by construction and must resolve to the FIRST)."""
+    E, N, A = mask.shape
+    want, plain = k10_oracle(d, pos, mask, gains32, communication)
+    gap = min_decision_gap(want, skip=tie_rows)
+    assert gap >= MIN_GAP, f"hand-built K10 input decides by {gap:.3e} < {MIN_GAP}"
+    action, util = pl.select(pl.dev_i32(pos), pl.dev_u8(mask), torch.from_numpy(gains32).to(pl.dev), communication)
+    for e, i in {(int(e), int(i)) for e, i, _ in np.argwhere(np.isnan(util) != np.isnan(want))}:
+        print(f"nan mismatch env {e} agent {i}: pos {pos[e].tolist()}\n mask {mask[e, i].tolist()}\n got  {util[e, i].tolist()}\n want {want[e, i].tolist()}")
+    assert np.array_equal(np.isnan(util), np.isnan(want)), np.argwhere(np.isnan(util) != np.isnan(want)).tolist()
+    ok = ~np.isnan(want)
+    bound = (A + 4) * 2.0 ** -24 * (np.abs(want) + 2 * np.abs(plain))
+    dev = np.abs(util.astype(np.float64) - want)
+    assert np.all(dev[ok] <= bound[ok]), (np.argwhere(ok & (dev > bound)).tolist(), float(np.nanmax(dev / bound)))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        chosen = np.argmax(want, axis=-1)     # (first nan, else first maximum)
+    assert np.array_equal(action, chosen), np.argwhere(action != chosen).tolist()
+    return want, plain, action, util
+
+
+def legal_masks(d, pos, rng=None, drop=0.0):
+    E, N, _ = pos.shape
+    mask = np.zeros((E, N, d.num_actions), dtype=np.uint8)
+    for e in range(E):
+        for i in range(N):
+            mask[e, i] = O.action_mask(d, pos[e, i]) != 0
+    if rng is not None and drop > 0:
+        mask &= (rng.random_sample(mask.shape) >= drop).astype(np.uint8)
+    return mask
+
+
+def random_gains(rng, mask):
+    """float32 gains of the size K9 produces, 0 where masked."""
+    return (rng.uniform(0.05, 1.0, size=mask.shape) * 0.02 * mask).astype(np.float32)
+
+
+def reseeded(build):
+    """build(rng) -> (pos, mask, gains, tie_rows); the first seed whose oracle gap holds is used (k10_check asserts it)."""
+    def run(d, communication):
+        for attempt in range(RESEEDS + 1):
+            pos, mask, gains, ties = build(np.random.RandomState(21 + attempt))
+            if min_decision_gap(k10_oracle(d, pos, mask, gains, communication)[0], skip=ties) >= MIN_GAP:
+                break
+        return pos, mask, gains, ties
+    return run
+
+
+@pytest.mark.parametrize("communication", [True, False])
+def test_k10_shared_lattice_points_and_order(communication):
+    """Four agents, 27 actions: three stand one lattice step apart on a row and one above the middle one (same altitude column), so
+    that many candidates of different agents land on the same lattice point -- (25, 25, 10) is claimed by all four.  The reference
+    discounts in place, agent by agent, and the last match wins: rows before i are already discounted when row i reads them."""
+    params = make_params("small", **A27)
+    d = O.Derived(params)
+    base = np.array([[20, 20, 10], [25, 20, 10], [30, 20, 10], [25, 20, 15]], dtype=np.int32)
+
+    def build(rng):
+        pos = np.stack([base, base, base[[2, 0, 3, 1]], base + np.array([0, 20, 0], dtype=np.int32)])
+        mask = legal_masks(d, pos)
+        mask[1] &= (rng.random_sample(mask[1].shape) >= 0.3).astype(np.uint8)      # env 1: holes in the masks
+        mask[3] &= (rng.random_sample(mask[3].shape) >= 0.5).astype(np.uint8)
+        return pos, mask, random_gains(rng, mask), ()
+
+    pos, mask, gains, _ = reseeded(build)(d, communication)
+    # the construction does what it says: a point claimed by several agents, one by (at least) three
+    claims = {}
+    for i in range(4):
+        for a in range(27):
+            if mask[0, i, a]:
+                claims.setdefault(tuple(O.action_to_position(d, pos[0, i], a)), set()).add(i)
+    assert len(claims[(25, 25, 10)]) == 4 and sum(len(v) >= 2 for v in claims.values()) >= 20
+    pl = Planner(params)
+    want, plain, _, _ = k10_check(pl, d, pos, mask, gains, communication)
+    if communication:
+        assert np.sum(np.abs(want - plain) > 1e-3 * plain) >= 100          # the discount is visible in the numbers
+        # ... and so is its order: the first-match-wins and the all-rows-raw variants give other numbers on these inputs
+        raw = np.array(plain[0])
+        first = raw.copy()
+        for i in range(4):
+            for a in range(27):
+                if not mask[0, i, a]:
+                    continue
+                p1 = tuple(O.action_to_position(d, pos[0, i], a))
+                hits = [(j, b) for j in range(4) for b in range(27) if j != i and mask[0, j, b] and tuple(O.action_to_position(d, pos[0, j], b)) == p1]
+                if hits:
+                    first[i, a] = raw[i, a] * (1 - first[hits[0][0], hits[0][1]])
+        assert np.sum(np.abs(first - want[0]) > 1e-4 * np.abs(want[0])) >= 5
+    else:
+        assert np.array_equal(want, plain)
+
+
+def test_k10_nan_rules():
+    """An agent whose gains are all zero has 0 / 0 = nan in every entry: its action is 0 (np.argmax takes the first nan); another
+    agent's candidate that shares a lattice point with one of its candidates inherits the nan and wins that agent's argmax."""
+    params = make_params("small", experiment__missions__n_agents=3, **A27)
+    d = O.Derived(params)
+    pos = np.array([[[20, 20, 10], [25, 20, 10], [40, 40, 10]],
+                    [[25, 20, 10], [20, 20, 10], [40, 40, 10]]], dtype=np.int32)
+    mask = legal_masks(d, pos)
+    rng = np.random.RandomState(5)
+    gains = random_gains(rng, mask)
+    gains[0, 1] = 0.0      # env 0: the middle agent (reads rows of agent 0 already discounted); env 1: the first one
+    gains[1, 0] = 0.0
+    pl = Planner(params)
+    for communication in (True, False):
+        want, _, action, util = k10_check(pl, d, pos, mask, gains, communication)
+        assert action[0, 1] == 0 and action[1, 0] == 0 and np.all(np.isnan(util[0, 1])) and np.all(np.isnan(util[1, 0]))
+        far = util[:, 2]
+        assert not np.any(np.isnan(far))                       # the far agent shares no point with anyone
+        if communication:
+            # agent 0 of env 0 shares points with the nan agent: its FIRST shared live candidate wins
+            row = util[0, 0]
+            assert np.isnan(row).any() and not np.isnan(row).all()
+            assert action[0, 0] == int(np.flatnonzero(np.isnan(row))[0]) and action[0, 0] != int(np.nanargmax(row))
+        else:
+            assert not np.any(np.isnan(util[0, 0])) and not np.any(np.isnan(util[1, 1]))
+
+
+@pytest.mark.parametrize("communication", [True, False])
+def test_k10_first_maximum_on_bit_equal_gains(communication):
+    """Bit-equal gains give bit-equal relative gains (same sum, same division) in float32 as in float64: the first of them wins.  The
+    agents stand too far apart to share a lattice point, so the discount does not touch the tie."""
+    params = make_params("small", experiment__missions__n_agents=3, **A27)
+    d = O.Derived(params)
+    pos = np.array([[[5, 5, 10], [25, 25, 10], [45, 45, 10]]] * 3, dtype=np.int32)
+    mask = legal_masks(d, pos)
+    rng = np.random.RandomState(8)
+    gains = random_gains(rng, mask)
+    ties = []
+    for e in range(3):
+        for i in range(3):
+            live = np.flatnonzero(mask[e, i])
+            pair = np.sort(rng.choice(live, size=2 + (e == 2), replace=False))
+            gains[e, i, pair] = np.float32(0.0301)             # above every random gain (<= 0.02): the tied entries are the maximum
+            ties.append((e * 3 + i, int(pair[0])))
+    pl = Planner(params)
+    _, _, action, _ = k10_check(pl, d, pos, mask, gains, communication, tie_rows=[r for r, _ in ties])
+    for r, first in ties:
+        assert action.reshape(-1)[r] == first
+
+
+@pytest.mark.parametrize("n_agents,over,envs", [(16, A27, 5), (2, A4, 7)])
+@pytest.mark.parametrize("communication", [True, False])
+def test_k10_team_sizes_and_batches(n_agents, over, envs, communication):
+    """The largest team (16 agents x 27 actions = 432 table entries for 64 lanes: seven trips of the set-up loop) packed one lattice
+    step apart, and the smallest (2 agents x 4 actions); several envs with different contents in one launch."""
+    params = make_params("small", experiment__missions__n_agents=n_agents, **over)
+    d = O.Derived(params)
+    z = 15 if d.space_z == 1 else 10
+
+    def build(rng):
+        pos = np.zeros((envs, n_agents, 3), dtype=np.int32)
+        for e in range(envs):
+            x0, y0 = 5 * int(rng.randint(0, 6)), 5 * int(rng.randint(0, 6))
+            cells = [(x0 + 5 * (k % 4), y0 + 5 * (k // 4), z if d.space_z == 1 else (10, 15, 5)[(k + e) % 3 if e % 2 else 0]) for k in range(16)]
+            order = rng.permutation(16)[:n_agents] if n_agents < 16 else rng.permutation(16)
+            if n_agents == 2:
+                order = [5, (7, 10, 13, 6, 0, 10, 15)[e]]   # two steps apart or diagonal: shared points; a direct neighbour and a far one: none
+            pos[e] = [cells[k] for k in order]
+        mask = legal_masks(d, pos, rng, drop=0.15)
+        return pos, mask, random_gains(rng, mask), ()
+
+    pos, mask, gains, _ = reseeded(build)(d, communication)
+    want, plain, _, _ = k10_check(Planner(params), d, pos, mask, gains, communication)
+    if communication:
+        assert np.sum(np.abs(want - plain) > 1e-3 * plain) >= (50 if n_agents == 16 else 4)
+
+
+# ---- at the batch size the planner is used at ----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("layout", ["rows", "tiles"])
+def test_ig_actions_at_1024_envs(layout):
+    """BASELINE config 2's shape with 27 actions, 1024 envs (COMATrainer.returns_on(.., "ig"), tools/learning_curve.py): after a few
+    uniform random steps, ig_actions on the full batch and on an 8-env batch holding eight of its envs agree bit for bit (the kernels
+    have no cross-env arithmetic and no atomics), every gain is finite, masked entries are exactly 0; three of the envs against the oracle, no tie excused."""
+    from ippmarl import _ffi
+    from ippmarl.vec_env import VecEnv, POLICY_UNIFORM
+    params = make_params("c2", **A27)
+    E = 1024
+    env = VecEnv(params, E, philox_seed=9, track_area=False, map_layout=layout)
+    assert env.tiled == (layout == "tiles")
+    env.reset(np.arange(1, E + 1))
+    for t in range(3):
+        env.steps(t, policy=POLICY_UNIFORM, features=False)
+    assert int(env.fault.abs().sum()) == 0
+    pick = np.array([1, 2, 3, E // 2 - 12, E // 2 - 11, (3 * E) // 4 + 9, E - 24, E]) - 1      # (test_full_size_properties' envs)
+    acts = env.ig_actions(communication=True)
+    gains, mask = env.ig_gains, env.ig_mask
+    assert bool(torch.isfinite(gains).all())
+    assert bool((bits(gains)[mask == 0] == 0).all()), "masked entries must be exactly +0.0"
+    small = VecEnv(params, 8, philox_seed=9, track_area=False, map_layout=layout)
+    idx = torch.from_numpy(pick).to(env.device)
+    small.local.copy_(env.local[idx])
+    small.pos.copy_(env.pos[idx])
+    acts8 = small.ig_actions(communication=True)
+    assert torch.equal(small.ig_mask, mask[idx])
+    assert torch.equal(bits(small.ig_gains), bits(gains[idx]))
+    assert torch.equal(acts8, acts[idx])
+    # three of them against the oracle: every gain at the tolerance, every decision the oracle's argmax -- no tie is excused
+    d = O.Derived(params)
+    d.exact = True
+    three = idx[[0, 3, 7]]
+    logodds = env.rows_view(env.local[three]).cpu().numpy()
+    pos, m, g, a = (x[three].cpu().numpy() for x in (env.pos, mask, gains, acts))
+    for e in range(3):
+        before = []
+        for i in range(d.n_agents):     # the mask ig_actions built is the reference's: boundary + collision against the agents before
+            legal = O.apply_collision_mask(d, pos[e, i], O.action_mask(d, pos[e, i]), before)
+            assert np.array_equal(m[e, i], (np.asarray(legal) != 0).astype(np.uint8))
+            before.append(pos[e, i])
+    want, plists = oracle_gains(d, logodds, pos, m)
+    np.testing.assert_allclose(g, want, rtol=RTOL, atol=ATOL)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        chosen = np.array([np.argmax(oracle_utilities(plists[e], want[e])[0], axis=-1) for e in range(3)])
+    assert np.array_equal(a, chosen), (a.tolist(), chosen.tolist())
+    with pytest.raises(_ffi.IppmError):
+        VecEnv(params, 4, track_area=False, map_layout=layout, team_sizes=[1, 2, 3, 4]).ig_actions()
+

@@ -311,11 +311,18 @@ def test_exact_mode_differs_only_by_reference_quantisation(golden, tag):
         assert deviating == sorted(tuple(c) for c in RQ.get((tag, key), [])), (tag, key, deviating)
 
 
-IG_CASES = {"ig_c1_e1": dict(name="c1", over={}), "ig_small3_e4": dict(name="small", over=dict(experiment__missions__n_agents=3))}
+IG_CASES = {"ig_c1_e1": dict(name="c1", over={}), "ig_small3_e4": dict(name="small", over=dict(experiment__missions__n_agents=3)),
+            # the reference's planner with 27 actions (three altitude layers) and with mapping.prior = 0.3 (update_cells' logit(prior))
+            "ig_small3_a27_e5": dict(name="small", over=dict(experiment__missions__n_agents=3, experiment__constraints__num_actions=27)),
+            "ig_small3_prior03_e6": dict(name="small", over=dict(experiment__missions__n_agents=3, mapping__prior=0.3))}
 
 
-def oracle_ig_run(fx, tag):
-    """The oracle's IG_baseline rerun from the draws the reference recorded: (execute()'s dict, the decidable F1 counts per evaluation)."""
+def oracle_ig_run(fx, tag, exact=False):
+    """The oracle's IG_baseline rerun from the draws the reference recorded: (execute()'s dict, the decidable F1 counts per evaluation).
+    ``exact``: the same run in exact float64 arithmetic (Derived.exact), kept on the recorded trajectory by flying the decisions of the
+    dtype-faithful run (which reproduces the recording's gains to the last digit, test_ig_baseline_replay)."""
+    if exact:
+        recorded_actions = oracle_ig_run(fx, tag)[0]["actions"]
     params = make_params(IG_CASES[tag]["name"], **IG_CASES[tag]["over"])
     n = params["experiment"]["missions"]["n_agents"]
     corr = unpack_correctness(fx)
@@ -325,10 +332,31 @@ def oracle_ig_run(fx, tag):
         # the reference draws in call order: n start sensings, then n per step
         return corr[s * n + i].reshape(shape)
 
-    ig = O.OracleIGBaseline(params, int(fx["episode"]), correctness, comm_draw=lambda i, j, t: comm[(t * n + i) * n + j])
+    ig = O.OracleIGBaseline(params, int(fx["episode"]), correctness, comm_draw=lambda i, j, t: comm[(t * n + i) * n + j], exact=exact,
+                            actions=(lambda i, t: recorded_actions[t][i]) if exact else None)
     with O.record_f1_counts() as counts:
         out = ig.execute()
     return out, counts
+
+
+def test_ig_recording_at_prior03_carries_reference_quantisation(golden):
+    """With mapping.prior != 0.5 every fusion shifts EVERY cell by -logit(prior) (mappings.py:109-124 on the full grid), so the maps
+    drift to the 0.9999 clip, where the reference's float32 re-quantisation of probabilities perturbs 1 - p by up to 2^-25 / 1e-4 =
+    3e-4 (conftest.REFERENCE_QUANTISATION_CELLS), and the planner's gains over such cells -- differences of nearly equal entropies --
+    inherit it.  The dtype-faithful oracle reproduces the recorded gains (test_ig_baseline_replay); exact float64 arithmetic on the SAME
+    trajectory differs from them by up to 6.1e-4 relative (34 of 270 gains beyond 1e-5), and left to its own argmax it leaves the recorded
+    trajectory at step 14.  So a device that computes in exact arithmetic is held to the exact run, not to the recording
+    (test_hip_dropin.py::test_ig_baseline_replays_reference_run); this test pins the two facts that justify it."""
+    tag = "ig_small3_prior03_e6"
+    fx = golden(tag)
+    out, _ = oracle_ig_run(fx, tag, exact=True)
+    assert np.array_equal(np.array(out["altitudes"]), fx["altitudes"])                     # the forced run is the recorded trajectory
+    got, want = np.array(out["gains"]), fx["gains"]
+    dev = np.abs(got - want) / np.maximum(np.abs(want), 1e-300)
+    dev[want == 0] = np.abs(got[want == 0])
+    assert 1e-4 < dev.max() < 2e-3, dev.max()      # reference noise: far beyond 1e-5, and still the same computation
+    assert np.median(dev[want != 0]) < 1e-6        # ... on a minority of the candidates
+    np.testing.assert_allclose(out["entropies"], fx["entropies"], rtol=1e-4)
 
 
 @pytest.mark.parametrize("tag", list(IG_CASES))

@@ -32,7 +32,7 @@ def main():
             ties += check(name, over, n_envs, seed=seed, first_episode=ep0, track_area=k % 4 != 1, fused_step=k % 8 == 5, team_sizes=teams)
             # every third case also through the greedy planner (K9 + K10) -- not above 15 m: the reference's planner divides by the
             # sensor noise, which its sensor model sets to 0 there (ZeroDivisionError in IG_baseline.py, as in the oracle)
-            if over.get("mapping__prior", 0.5) == 0.5 and k % 3 == 0 and over.get("experiment__constraints__max_altitude", 15) <= 15:
+            if k % 3 == 0 and over.get("experiment__constraints__max_altitude", 15) <= 15:
                 check_ig(name, over, seed=seed & 0xFFFFFFFF, first_episode=ep0, n_envs=n_envs)
         except Exception as exc:
             msg = str(exc)
