@@ -81,7 +81,8 @@ k_area_sums(const float* __restrict__ maps, double* __restrict__ area, int gx, i
 // shared pieces of the two feature kernels (workgroups of K6_THREADS threads)
 // ------------------------------------------------------------------------------------------------------
 #define K6_THREADS 128
-#define BIN_WORDS 4  // a column bin spans at most ceil(gy/11) + 1 cells: 128-cell masks cover grids up to 1397 cells wide
+#define BIN_WORDS 4  // 128-cell masks: every column bin fits (bin_cells() <= 32 BIN_WORDS) for grids up to 1398 cells wide and for 1408 = 11 * 128;
+                     // 1399 .. 1407 and everything from 1409 on have a bin of 129 cells or more.  feature_checks rejects those grids
 
 struct RectList {  // in LDS
   int r[IPPM_MAX_AGENTS][4];   // [yu,yd,xl,xr]
@@ -402,6 +403,12 @@ __global__ void k_entropy_maps(const ippm_config* __restrict__ c, const float* _
 static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int grid1(size_t n, int b = 256) { return (int)((n + b - 1) / b); }
 
+// cells that column bin `bin` of an axis of n cells touches (its first and last cell may belong to it only in part)
+static inline int bin_cells(int bin, int n) {
+  const long long lo = (long long)bin * n / IPPM_FEAT, hi = ((long long)(bin + 1) * n + IPPM_FEAT - 1) / IPPM_FEAT;
+  return (int)(std::min<long long>(n, hi) - lo);
+}
+
 static int feature_checks(const ippm_ctx* ctx, const char* who) {
   const ippm_config& c = ctx->cfg;
   if (c.space_x != IPPM_FEAT || c.space_y != IPPM_FEAT) {
@@ -412,6 +419,16 @@ static int feature_checks(const ippm_ctx* ctx, const char* who) {
   for (int k = 0; k < c.space_z; ++k) {
     if (c.radius_x[k] != c.radius_y[k]) { ippm_set_error(std::string(who) + ": needs a square field of view"); return -2; }
     if (2 * c.radius_x[k] < IPPM_FEAT) { ippm_set_error(std::string(who) + ": footprint image smaller than 11 cells"); return -2; }
+  }
+  // the footprint-indicator planes (6 and 10) hold the cells of a column bin in a mask of 32 BIN_WORDS bits (indicator_plane; along x
+  // the slabs need no masks): a wider bin would silently lose its cells beyond the mask
+  int widest = 0;
+  for (int b = 0; b < IPPM_FEAT; ++b) widest = std::max(widest, bin_cells(b, c.grid_y));
+  if (widest > 32 * BIN_WORDS) {
+    ippm_set_error(std::string(who) + ": grid_y = " + std::to_string(c.grid_y) + " has a feature bin of " + std::to_string(widest) +
+                   " cells; the footprint planes hold at most " + std::to_string(32 * BIN_WORDS) + " cells per bin (every grid_y up to " +
+                   std::to_string(IPPM_FEAT * (32 * BIN_WORDS - 1) + 1) + " fits, and " + std::to_string(IPPM_FEAT * 32 * BIN_WORDS) + ")");
+    return -2;
   }
   return 0;
 }

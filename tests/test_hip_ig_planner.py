@@ -206,13 +206,13 @@ def build_masks(d, pos, rng):
     return mask
 
 
-def build_maps(d, lc, E, rng):
-    """float32 log-odds [E, N, gx, gy], every agent its own: the prior, with blobs of observed cells (p in 0.02 .. 0.98, cell by
+def build_maps(d, lc, E, rng, n_agents=None):
+    """float32 log-odds [E, N, gx, gy] (N = ``n_agents``, by default the team's size), every agent its own: the prior, with blobs of observed cells (p in 0.02 .. 0.98, cell by
     cell), saturated cells (+-clip exactly), cells BEYOND the clip (the deferred clamp leaves such cells in the local maps) and at
     +-inf; map (0, 0) is saturated everywhere (a candidate over nothing but saturated cells: its gain is made of differences of
     entropies that nearly cancel, DESIGN.md "What the random sweeps found": such gains are 1e-9 .. 1e-7 in size and held by the
     tolerance's absolute 1e-9 alone)."""
-    N, gx, gy = d.n_agents, int(d.gx), int(d.gy)
+    N, gx, gy = d.n_agents if n_agents is None else int(n_agents), int(d.gx), int(d.gy)
     lc = np.float32(lc)
     maps = np.full((E, N, gx, gy), np.float32(np.log(d.prior / (1 - d.prior))), dtype=np.float32)
 
