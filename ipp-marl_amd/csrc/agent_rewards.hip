@@ -16,9 +16,6 @@
 // hand-off.  Under tile storage the lanes walk whole tiles: 8 consecutive lanes = the 2 groups x 4 rows of one 128-byte tile.
 #include "ippm_tiles.h"
 
-typedef unsigned ippm_ar_u4 __attribute__((ext_vector_type(4)));
-#define IPPM_AR_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
-#define IPPM_AR_OOB 0x7FFFFFF0
 #define IPPM_AR_THREADS 256
 #define IPPM_AR_UNR 4   // cell groups in flight per lane
 
@@ -53,13 +50,13 @@ __global__ __launch_bounds__(IPPM_AR_THREADS) void k_agent_rewards(const ippm_co
   const int rows = xb - x0;
   const int items = TL ? ((rows + 3) >> 2) * groups * 4 : rows * groups;
   const float inv_groups = __builtin_amdgcn_rcpf((float)max(groups, 1));
-  const __amdgpu_buffer_rsrc_t rmap = IPPM_AR_RSRC(global + (size_t)e * IPPM_MAP_PITCH(gx, gy), (size_t)gx * gy * 4);
+  const __amdgpu_buffer_rsrc_t rmap = IPPM_RSRC(global + (size_t)e * IPPM_MAP_PITCH(gx, gy), (size_t)gx * gy * 4);
   const size_t TB = ippm_tile_bytes(S, VEC);
-  const __amdgpu_buffer_rsrc_t rcode = IPPM_AR_RSRC(code + (size_t)ei * TB, TB);
+  const __amdgpu_buffer_rsrc_t rcode = IPPM_RSRC(code + (size_t)ei * TB, TB);
   const int tile_y0 = yu & ~3;
   double a1 = 0.0, aD = 0.0;   // float64 lane sums of w(a) (H(b) - H(a)) and (w(a) - w(b)) H(b)
   for (int base = threadIdx.x; base < items; base += IPPM_AR_THREADS * IPPM_AR_UNR) {
-    float v[IPPM_AR_UNR][VEC];
+    CellVec<VEC> v[IPPM_AR_UNR];
     uint32_t bits[IPPM_AR_UNR];
     int xs[IPPM_AR_UNR], ys[IPPM_AR_UNR];
     bool ok[IPPM_AR_UNR];
@@ -79,17 +76,11 @@ __global__ __launch_bounds__(IPPM_AR_THREADS) void k_agent_rewards(const ippm_co
       const int y = y0 + g * VEC;
       const bool valid = it < items && x >= xa && x < xb;
       xs[u] = x; ys[u] = y; ok[u] = valid;
-      const int off = valid ? ippm_cell_index(x, y, gy, TL ? 1 : 0) * 4 : IPPM_AR_OOB;
-      if (VEC == 4) {
-        const ippm_ar_u4 t = __builtin_amdgcn_raw_buffer_load_b128(rmap, off, 0, 0);
-        v[u][0] = __uint_as_float(t.x); v[u][1 % VEC] = __uint_as_float(t.y);
-        v[u][2 % VEC] = __uint_as_float(t.z); v[u][3 % VEC] = __uint_as_float(t.w);
-      } else {
-        v[u][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmap, off, 0, 0));
-      }
+      const int off = valid ? ippm_cell_index(x, y, gy, TL ? 1 : 0) * 4 : IPPM_OOB;
+      v[u] = buf_load_cells<VEC>(rmap, off);
       // the group's measurement bits, for a group that meets the footprint
       const bool meets = valid && fp && (unsigned)(x - xl) < (unsigned)h && y + VEC > yu && y < yd;
-      bits[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rcode, meets ? (int)tile_index<VEC>(x - xl, y - tile_y0, S) : IPPM_AR_OOB, 0, 0) &
+      bits[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rcode, meets ? (int)tile_index<VEC>(x - xl, y - tile_y0, S) : IPPM_OOB, 0, 0) &
                 (VEC == 4 ? 0xFu : 1u);
     }
 #pragma unroll
@@ -103,7 +94,7 @@ __global__ __launch_bounds__(IPPM_AR_THREADS) void k_agent_rewards(const ippm_co
         for (int q = 0; q < VEC; ++q) {
           if (!ok[u] || y + q >= gy) continue;
           const bool in = rowin && (unsigned)(y + q - yu) < (unsigned)w;
-          const float b = v[u][q];
+          const float b = v[u].v[q];
           const double kc = fmin(fmax((double)b, -(double)lc), (double)lc);
           const float a = (float)(kc + (in ? (double)(((bits[u] >> q) & 1u) ? lm1 : lm0) : -lp64));
           const float wa = ippm_weight_l(a, wt), wb = ippm_weight_l(b, wt);
@@ -119,9 +110,9 @@ __global__ __launch_bounds__(IPPM_AR_THREADS) void k_agent_rewards(const ippm_co
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
           const bool in = rowin && (unsigned)(y + q - yu) < (unsigned)w;
-          av[q] = ippm_clampl(v[u][q], lc) + (((bits[u] >> q) & 1u) ? lm1 : lm0);
+          av[q] = ippm_clampl(v[u].v[q], lc) + (((bits[u] >> q) & 1u) ? lm1 : lm0);
           wa[q] = in ? ippm_weight_l(av[q], wt) : 0.f;
-          wb[q] = in ? ippm_weight_l(v[u][q], wt) : 0.f;
+          wb[q] = in ? ippm_weight_l(v[u].v[q], wt) : 0.f;
           wsum += wa[q] + wb[q];
         }
         // groups whose cells are believed free before and after (all weights 0) skip the entropies: wave-uniform on coherent terrain
@@ -129,7 +120,7 @@ __global__ __launch_bounds__(IPPM_AR_THREADS) void k_agent_rewards(const ippm_co
           float r1 = 0.f, rD = 0.f;
 #pragma unroll
           for (int q = 0; q < VEC; ++q) {
-            const float hb = ippm_entropy_l(v[u][q], lc), ha = ippm_entropy_l(av[q], lc);
+            const float hb = ippm_entropy_l(v[u].v[q], lc), ha = ippm_entropy_l(av[q], lc);
             r1 += wa[q] * (hb - ha);
             rD += (wa[q] - wb[q]) * hb;
           }

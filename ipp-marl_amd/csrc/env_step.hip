@@ -293,9 +293,6 @@ k_sense_update(const ippm_config* __restrict__ c, const int64_t* __restrict__ ep
 // through raw buffer resources (one VALU per address; a lane without work points out of range: loads return 0, stores
 // are dropped), per-cell selects are bit-mask blends, the clip is one v_med3.
 // ------------------------------------------------------------------------------------------------------
-typedef unsigned ippm_k3_u4 __attribute__((ext_vector_type(4)));
-#define IPPM_K3_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
-#define IPPM_K3_OOB 0x7FFFFFF0
 #define IPPM_K3_WAVES 4       // wavefronts per workgroup of k_sense_tiles
 #define IPPM_K3_CH 3          // loads in flight per lane of k_sense_tiles
 #define IPPM_K3_GRID_ORDER 0  // default workgroup order of k_sense_tiles (template parameter GO)
@@ -418,10 +415,10 @@ k_sense_tiles(const int32_t* __restrict__ rect_in, int n, int agent_sel, int sta
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int sub = lane >> shift, gl = lane & (lpr - 1);
   const size_t TB = ippm_tile_bytes(S, VEC);
-  const __amdgpu_buffer_rsrc_t rmap = IPPM_K3_RSRC(local + (size_t)(e * n + i) * IPPM_MAP_PITCH(gx, gy), (size_t)gx * gy * 4);
-  const __amdgpu_buffer_rsrc_t rtruth = IPPM_K3_RSRC(truth + (size_t)e * ippm_truth_bytes(gx, gy), ippm_truth_bytes(gx, gy));
-  const __amdgpu_buffer_rsrc_t rcode = IPPM_K3_RSRC(code + (size_t)(e * n + i) * TB, TB);
-  const __amdgpu_buffer_rsrc_t rflip = IPPM_K3_RSRC(FLIPS ? flips + (size_t)(e * n + i) * TB : code, FLIPS ? TB : 0);
+  const __amdgpu_buffer_rsrc_t rmap = IPPM_RSRC(local + (size_t)(e * n + i) * IPPM_MAP_PITCH(gx, gy), (size_t)gx * gy * 4);
+  const __amdgpu_buffer_rsrc_t rtruth = IPPM_RSRC(truth + (size_t)e * ippm_truth_bytes(gx, gy), ippm_truth_bytes(gx, gy));
+  const __amdgpu_buffer_rsrc_t rcode = IPPM_RSRC(code + (size_t)(e * n + i) * TB, TB);
+  const __amdgpu_buffer_rsrc_t rflip = IPPM_RSRC(FLIPS ? flips + (size_t)(e * n + i) * TB : code, FLIPS ? TB : 0);
   const uint32_t sw = ippm_stream_word((uint32_t)i, (uint32_t)stage, IPPM_DOMAIN_FLIP);
   float amax = 0.f;
   for (int gbase = 0; gbase < (DENSE ? 1 : groups); gbase += CH * lpr) {     // one trip unless the footprint is wider than 3 x 64 groups
@@ -439,10 +436,11 @@ k_sense_tiles(const int32_t* __restrict__ rect_in, int n, int agent_sel, int sta
           const int T = dense_base + q * 64 + lane;
           const int rr = ippm_div_small(T, dense_invw);
           const int gi = T - rr * groups;
-          row = ((tr0 + rr) << 2) + ((gi >> 1) & 3) - xl;      // (may lie outside [0, h): an edge tile's rows beyond the footprint)
+          const ippm_lane_load ll = ippm_tile_lane_load(tr0 + rr, y0 + gi, gy);   // (y0 = 8 x the first tile = its first lane-load)
+          row = ll.row - xl;      // (may lie outside [0, h): an edge tile's rows beyond the footprint)
           on[q] = T < dense_total;
-          y = y0 + ((gi >> 3) << 3) + ((gi & 1) << 2);
-          poff[q] = ((tr0 + rr) * gy + y0 + gi) * 16;   // a row of tiles is 16 gy bytes, tile c of it at 128 c = 16 (8 c) bytes, lane-load g of the row of tiles at 16 g
+          y = ll.col;
+          poff[q] = ll.off;
         } else if (DENSE) {
           const int T = dense_base + q * 64 + lane;
           const int rr = ippm_div_small(T, dense_invw);
@@ -460,17 +458,11 @@ k_sense_tiles(const int32_t* __restrict__ rect_in, int n, int agent_sel, int sta
         const int cell = x * gy + y;
         cellv[q] = cell; rowv[q] = row; yv[q] = y;
         if (!TL) poff[q] = cell * 4;
-        if (VEC == 4) {
-          const ippm_k3_u4 t = __builtin_amdgcn_raw_buffer_load_b128(rmap, on[q] ? poff[q] : IPPM_K3_OOB, 0, 0);
-          m[q].v[0] = __uint_as_float(t.x); m[q].v[1 % VEC] = __uint_as_float(t.y);
-          m[q].v[2 % VEC] = __uint_as_float(t.z); m[q].v[3 % VEC] = __uint_as_float(t.w);
-        } else {
-          m[q].v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmap, on[q] ? cell * 4 : IPPM_K3_OOB, 0, 0));
-        }
+        m[q] = buf_load_cells<VEC>(rmap, on[q] ? poff[q] : IPPM_OOB);
         // (grids not a multiple of 4 wide: a group's four truth bits may straddle a byte -- two bytes at any byte address)
-        tw[q] = mis ? (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rtruth, on[q] ? (cell >> 3) : IPPM_K3_OOB, 0, 0)
-                    : (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rtruth, on[q] ? (cell >> 3) : IPPM_K3_OOB, 0, 0);
-        fw[q] = FLIPS ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rflip, on[q] && (!TL || (unsigned)row < (unsigned)h) ? (int)tile_index<VEC>(row, y - tile_y0, S) : IPPM_K3_OOB, 0, 0)
+        tw[q] = mis ? (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rtruth, on[q] ? (cell >> 3) : IPPM_OOB, 0, 0)
+                    : (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rtruth, on[q] ? (cell >> 3) : IPPM_OOB, 0, 0);
+        fw[q] = FLIPS ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rflip, on[q] && (!TL || (unsigned)row < (unsigned)h) ? (int)tile_index<VEC>(row, y - tile_y0, S) : IPPM_OOB, 0, 0)
                       : 0u;
       }
 #pragma unroll
@@ -501,49 +493,22 @@ k_sense_tiles(const int32_t* __restrict__ rect_in, int n, int agent_sel, int sta
         if (TL) inm = (unsigned)row < (unsigned)h ? inm : 0u;   // ... and rows (an edge tile's rows above / below the footprint)
         const uint32_t obs = (tbits ^ flipbits) & inm;
         // mappings.py:109-124 in log-odds: clip the prior belief, add the measurement's log-odds (minus logit(prior))
+        CellVec<VEC> nv;
         float dsig[VEC];
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
           const float old = m[q].v[j];
           const float l = ippm_clampl(old, lc) + ippm_blend(ippm_bitmask(obs, j), lm1, lm0);
           const uint32_t im = ippm_bitmask(inm, j);
-          m[q].v[j] = ippm_blend(im, l, old);
+          nv.v[j] = ippm_blend(im, l, old);
           amax = fmaxf(amax, fabsf(ippm_masked(im, l)));
-          if (TRACK) dsig[j] = sigmoid_diff(m[q].v[j], old);   // (exactly 0 for the cells outside the footprint's columns)
+          if (TRACK) dsig[j] = sigmoid_diff(nv.v[j], old);   // (exactly 0 for the cells outside the footprint's columns)
         }
-        if (TRACK && VEC == 4 && on[q]) {
-          float sd = 0.f, cA = 0.f;
-          const AreaCols<VEC> ac = area_cols<VEC>(y, gy, inv_gy);
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) { sd += dsig[j]; cA += ac.wA[j] * dsig[j]; }
-          const float cB = 11.f * sd - cA;
-          const int n11 = 11 * (xl + row), rb = area_bin(n11, inv_gx);
-          const float nA = (float)min((rb + 1) * gx - n11, 11), nB = 11.f - nA;
-          double* pa = s_area + rb * IPPM_AREA_LD + ac.cb;
-          const float v00 = nA * cA, v01 = nA * cB, v10 = nB * cA, v11 = nB * cB;
-          if (v00 != 0.f) atomicAdd(pa, (double)v00);
-          if (v01 != 0.f) atomicAdd(pa + 1, (double)v01);
-          if (v10 != 0.f) atomicAdd(pa + IPPM_AREA_LD, (double)v10);
-          if (v11 != 0.f) atomicAdd(pa + IPPM_AREA_LD + 1, (double)v11);
-        }
-        const int off = on[q] ? poff[q] : IPPM_K3_OOB;
-        if (VEC == 4) {
-          ippm_k3_u4 t;
-          t.x = __float_as_uint(m[q].v[0]); t.y = __float_as_uint(m[q].v[1 % VEC]);
-          t.z = __float_as_uint(m[q].v[2 % VEC]); t.w = __float_as_uint(m[q].v[3 % VEC]);
-          // the last group of a row that is not a multiple of 4 wide hangs over into the next row: its cells go out one by one
-          const bool tail = mis && y + 4 > gy;
-          __builtin_amdgcn_raw_buffer_store_b128(t, rmap, tail ? IPPM_K3_OOB : off, 0, 0);
-          if (mis) {
-            __builtin_amdgcn_raw_buffer_store_b32(t.x, rmap, tail ? off : IPPM_K3_OOB, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(t.y, rmap, tail && y + 1 < gy ? off + 4 : IPPM_K3_OOB, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(t.z, rmap, tail && y + 2 < gy ? off + 8 : IPPM_K3_OOB, 0, 0);
-          }
-        } else {
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(m[q].v[0]), rmap, off, 0, 0);
-        }
+        if (TRACK && VEC == 4 && on[q]) area_slot_add(gx, gy, inv_gx, inv_gy, s_area, xl + row, y, dsig);
+        // (the last group of a row that is not a multiple of 4 wide hangs over into the next row: its cells go out one by one)
+        buf_store_cells_tail<VEC, MIS>(rmap, on[q] ? poff[q] : IPPM_OOB, y, gy, nv);
         // (a group outside the footprint's columns -- rounded row segments -- has no byte in the code tile)
-        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)obs, rcode, on[q] && inm != 0 ? (int)tile_index<VEC>(row, y - tile_y0, S) : IPPM_K3_OOB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)obs, rcode, on[q] && inm != 0 ? (int)tile_index<VEC>(row, y - tile_y0, S) : IPPM_OOB, 0, 0);
       }
       if (DENSE) break;   // (a part is exactly one trip of its four wavefronts)
     }
@@ -597,7 +562,7 @@ k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ epis
   }
   const float lp = c->logit_prior;
   float* map = is_global ? global + (size_t)e * IPPM_MAP_PITCH(gx, gy) : local + (size_t)(e * n + m) * IPPM_MAP_PITCH(gx, gy);
-  const __amdgpu_buffer_rsrc_t rmap = IPPM_K3_RSRC(map, (size_t)gx * gy * 4);
+  const __amdgpu_buffer_rsrc_t rmap = IPPM_RSRC(map, (size_t)gx * gy * 4);
   const bool mis = (gy & 3) != 0;
   const int fg0 = yu >> 2, fg1 = (yd + 3) >> 2;   // groups that meet the footprint's columns
   if ((int)blockIdx.x < fill_chunks) {
@@ -641,7 +606,7 @@ k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ epis
       }
     }
     if (by1 <= by0) return;
-    const ippm_k3_u4 t = {__float_as_uint(lp), __float_as_uint(lp), __float_as_uint(lp), __float_as_uint(lp)};
+    const CellVec<4> pv = {{lp, lp, lp, lp}};
     // a wavefront takes IPPM_RESET_ROWS / 4 consecutive rows, a lane one 16-byte store in each of them (all in flight together)
     constexpr int RPW = IPPM_RESET_ROWS / 4;
     const int xw = blockIdx.x * IPPM_RESET_ROWS + wv * RPW;
@@ -659,7 +624,7 @@ k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ epis
         const bool fp_row = fp_some && R >= fR0 && R < fR1;
         for (int G = G0 + lane; G < G1; G += 64) {
           const bool skip = fp_row && G >= fG0 && G < fG1;
-          __builtin_amdgcn_raw_buffer_store_b128(t, rmap, skip ? IPPM_K3_OOB : (R * gy + G) * 16, 0, 2);
+          buf_store_cells<4, 2>(rmap, skip ? IPPM_OOB : ippm_tile_lane_load(R, G, gy).off, pv);
         }
       }
       return;
@@ -675,12 +640,12 @@ k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ epis
         const int off = (x * gy + y) * 4;
         if (mis && y + 4 > gy) {   // a row's last group hangs over into the next row: cell by cell
           if (!skip) {
-            __builtin_amdgcn_raw_buffer_store_b32(t.x, rmap, off, 0, 0);
-            if (y + 1 < gy) __builtin_amdgcn_raw_buffer_store_b32(t.x, rmap, off + 4, 0, 0);
-            if (y + 2 < gy) __builtin_amdgcn_raw_buffer_store_b32(t.x, rmap, off + 8, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lp), rmap, off, 0, 0);
+            if (y + 1 < gy) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lp), rmap, off + 4, 0, 0);
+            if (y + 2 < gy) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lp), rmap, off + 8, 0, 0);
           }
         } else {
-          __builtin_amdgcn_raw_buffer_store_b128(t, rmap, skip ? IPPM_K3_OOB : off, 0, 2);   // non-temporal: read a step later at the earliest
+          buf_store_cells<4, 2>(rmap, skip ? IPPM_OOB : off, pv);   // non-temporal: read a step later at the earliest
         }
       }
     }
@@ -701,16 +666,17 @@ k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ epis
   const uint32_t sw = ippm_stream_word((uint32_t)m, 0u, IPPM_DOMAIN_FLIP);
   const int64_t ep = episode ? episode[e] : 0;
   const uint32_t k0 = (uint32_t)c->philox_seed, k1 = (uint32_t)(c->philox_seed >> 32);
-  const __amdgpu_buffer_rsrc_t rtruth = IPPM_K3_RSRC(truth + (size_t)e * ippm_truth_bytes(gx, gy), ippm_truth_bytes(gx, gy));
+  const __amdgpu_buffer_rsrc_t rtruth = IPPM_RSRC(truth + (size_t)e * ippm_truth_bytes(gx, gy), ippm_truth_bytes(gx, gy));
   const size_t TB = ippm_tile_bytes(S, 4);
-  const __amdgpu_buffer_rsrc_t rcode = IPPM_K3_RSRC(code + (size_t)(e * n + m) * TB, TB);
-  const __amdgpu_buffer_rsrc_t rflip = IPPM_K3_RSRC(flips ? flips + (size_t)(e * n + m) * TB : code, flips ? TB : 0);
+  const __amdgpu_buffer_rsrc_t rcode = IPPM_RSRC(code + (size_t)(e * n + m) * TB, TB);
+  const __amdgpu_buffer_rsrc_t rflip = IPPM_RSRC(flips ? flips + (size_t)(e * n + m) * TB : code, flips ? TB : 0);
   if (tl) {
     // every tile the footprint meets, whole: a wavefront takes rows of tiles, its lanes their lane-loads; cells outside the footprint get the prior
     const int G0 = (yu >> 3) << 3, G1 = ((yd + 7) >> 3) << 3, y0c = yu & ~3;
     for (int R = ((xl + r0) >> 2) + wv; R * 4 < xl + r1; R += 4) {
       for (int G = G0 + lane; G < G1; G += 64) {
-        const int x = (R << 2) + ((G >> 1) & 3), y = ((G >> 3) << 3) + ((G & 1) << 2);
+        const ippm_lane_load ll = ippm_tile_lane_load(R, G, gy);
+        const int x = ll.row, y = ll.col;
         const int row = x - xl;
         const int cell = x * gy + y;
         const uint32_t tw = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rtruth, cell >> 3, 0, 0);
@@ -723,12 +689,10 @@ k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ epis
         if (flips) flipbits = inm ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rflip, (int)tile_index<4>(row, y - y0c, S), 0, 0) & 0xFu : 0u;
         else flipbits = philox_flip_bits4((uint32_t)cell, (uint32_t)ep, sw, (uint32_t)(ep >> 32), k0, k1, thr, false);
         const uint32_t obs = (tbits ^ flipbits) & inm;
-        float v[4];
+        CellVec<4> v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = ((inm >> j) & 1u) ? ippm_clampl(lp, lc) + (((obs >> j) & 1u) ? lm1 : lm0) : lp;
-        ippm_k3_u4 t;
-        t.x = __float_as_uint(v[0]); t.y = __float_as_uint(v[1]); t.z = __float_as_uint(v[2]); t.w = __float_as_uint(v[3]);
-        __builtin_amdgcn_raw_buffer_store_b128(t, rmap, (R * gy + G) * 16, 0, 0);
+        for (int j = 0; j < 4; ++j) v.v[j] = ((inm >> j) & 1u) ? ippm_clampl(lp, lc) + (((obs >> j) & 1u) ? lm1 : lm0) : lp;
+        buf_store_cells<4>(rmap, ll.off, v);
         if (inm) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)obs, rcode, (int)tile_index<4>(row, y - y0c, S), 0, 0);
       }
     }
@@ -762,7 +726,8 @@ k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ epis
 #pragma unroll
         for (int j = 0; j < 4; ++j)   // mappings.py:109-124 on a prior cell, exactly as K3 forms it; the group's other cells: prior
           v[j] = ((inm >> j) & 1u) ? ippm_clampl(lp, lc) + (((obs >> j) & 1u) ? lm1 : lm0) : lp;
-        ippm_k3_u4 t;
+        // (packed by hand, ahead of the branch: through buf_store_cells the kernel takes 41 registers for 39)
+        ippm_u4 t;
         t.x = __float_as_uint(v[0]); t.y = __float_as_uint(v[1]); t.z = __float_as_uint(v[2]); t.w = __float_as_uint(v[3]);
         const int off = cell * 4;
         if (mis && y + 4 > gy) {

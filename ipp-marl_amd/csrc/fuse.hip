@@ -29,9 +29,6 @@
 // empty asm: makes a loop-invariant value look loop-variant to the optimiser (no instruction is emitted)
 #define IPPM_OPAQUE(x) asm volatile("" : "+v"(x))
 
-__device__ __forceinline__ int lane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-__device__ __forceinline__ float lane_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-
 struct OpTable {   // lane o holds op o of the plan (zeros beyond the plan: an empty rectangle that never covers anything)
   int yu, yd;
   int cs;          // uniform part of the op's code byte offsets (see walk_slab); out of range for ops without bits
@@ -40,11 +37,6 @@ struct OpTable {   // lane o holds op o of the plan (zeros beyond the plan: an e
 struct SlabTable { // lane s holds slab s of the plan
   int xa, xb, active, hull;
 };
-
-typedef unsigned ippm_u4 __attribute__((ext_vector_type(4)));
-// raw buffer resources (gfx9 family descriptor word 3 = 0x00020000): uniform base + per-lane 32-bit byte offset, one VALU
-// per address instead of a 64-bit multiply-add chain, and loads past the end return 0 instead of faulting
-#define IPPM_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
 
 struct WaveCtx {   // what a wave needs while it walks its rows
   __amdgpu_buffer_rsrc_t map;    // this map: gx * gy floats
@@ -70,28 +62,6 @@ struct WaveAcc {
 };
 
 // (entropy_l_f64, the SHIFT path's float64 entropy: ippm_internal.h, shared with k_agent_rewards)
-
-template <int VEC>
-__device__ __forceinline__ CellVec<VEC> buf_load_cells(__amdgpu_buffer_rsrc_t r, int off) {
-  CellVec<VEC> c;
-  if (VEC == 4) {
-    const ippm_u4 t = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-    c.v[0] = __uint_as_float(t.x); c.v[1 % VEC] = __uint_as_float(t.y); c.v[2 % VEC] = __uint_as_float(t.z); c.v[3 % VEC] = __uint_as_float(t.w);
-  } else {
-    c.v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-  }
-  return c;
-}
-template <int VEC>
-__device__ __forceinline__ void buf_store_cells(__amdgpu_buffer_rsrc_t r, int off, const CellVec<VEC>& c) {
-  if (VEC == 4) {
-    ippm_u4 t;
-    t.x = __float_as_uint(c.v[0]); t.y = __float_as_uint(c.v[1 % VEC]); t.z = __float_as_uint(c.v[2 % VEC]); t.w = __float_as_uint(c.v[3 % VEC]);
-    __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, 0);
-  } else {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c.v[0]), r, off, 0, 0);
-  }
-}
 
 // Rows [x, xe) of one slab with the ops of `set` (bit o = op o), at most NA of them.
 // Each of the rpw sub-rows of the wavefront takes a contiguous block of the slab's rows and keeps FU consecutive rows in
@@ -216,18 +186,10 @@ __device__ __forceinline__ void walk_slab(const WaveCtx& w, const OpTable& t, Wa
           if (TRACK) d[q] = valid && (!SHIFT || ((vm >> q) & 1u)) ? sigmoid_diff(a, bsave[q]) : 0.f;
         }
         {
-          const int soff = valid ? (w.tl ? ippm_cell_index(row, y, w.gy, 1) * 4 : row * gybyte + ybyte) : 0x7FFFFFF0;
-          if (VEC == 4 && (w.gy & 3) != 0) {
-            // (uniform) rows are not a multiple of 4 wide: the last group of a row hangs over into the next row -- its cells go
-            // out one by one, another lane owns the rest
-            const bool tail = y + 4 > w.gy;
-            buf_store_cells<VEC>(w.map, tail ? 0x7FFFFFF0 : soff, mv);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[0]), w.map, tail ? soff : 0x7FFFFFF0, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[1 % VEC]), w.map, tail && y + 1 < w.gy ? soff + 4 : 0x7FFFFFF0, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mv.v[2 % VEC]), w.map, tail && y + 2 < w.gy ? soff + 8 : 0x7FFFFFF0, 0, 0);
-          } else {
-            buf_store_cells<VEC>(w.map, soff, mv);
-          }
+          const int soff = valid ? (w.tl ? ippm_cell_index(row, y, w.gy, 1) * 4 : row * gybyte + ybyte) : IPPM_OOB;
+          // (uniform) rows that are not a multiple of 4 wide: the row's last group goes out cell by cell
+          if (VEC == 4 && (w.gy & 3) != 0) buf_store_cells_tail<VEC, true>(w.map, soff, y, w.gy, mv);
+          else buf_store_cells<VEC>(w.map, soff, mv);
         }
         if (TRACK) area_row<VEC>(acc, w.s_area, ac, min(row, re - 1), w.gx, w.inv_gx, d);
         if (w.is_global) {

@@ -21,13 +21,7 @@
 
 #include "ippm_tiles.h"
 
-typedef unsigned ippm_t_u4 __attribute__((ext_vector_type(4)));
-#define IPPM_T_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
-#define IPPM_T_OOB 0x7FFFFFF0
 #define IPPM_T_FAR (-(1 << 20))   // column of a lane-load past the item's end: no op covers it
-
-__device__ __forceinline__ int t_lane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-__device__ __forceinline__ float t_lane_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 
 struct TileCtx {
   float* local;
@@ -45,32 +39,8 @@ struct TileCtx {
   float inv_gx, inv_gy;
 };
 
-// The item's contribution to the area sums of its map: per lane-load the weighted sigmoid differences of its four cells into
-// the (at most) 2 x 2 bins the group meets.  `old4` / `new4`: the cells as loaded and as stored (a lane-load past the item's
-// end loaded zeros and stores nothing: zero difference).
-// MIS (rows not a multiple of 4 wide): the cells of a row's last group that hang over into the next row were loaded and run through
-// the chain but are never stored (another lane owns them): they contribute nothing here either.
-template <bool MIS>
-__device__ __forceinline__ void tile_area_slot(const TileCtx& w, int x, int y, const float* old4, const float* new4) {
-  float d[4], sd = 0.f, cA = 0.f;
-  const AreaCols<4> ac = area_cols<4>(y, w.gy, w.inv_gy);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    d[j] = (MIS && y + j >= w.gy) ? 0.f : sigmoid_diff(new4[j], old4[j]);
-    sd += d[j];
-    cA += ac.wA[j] * d[j];
-  }
-  const float cB = 11.f * sd - cA;
-  const int n11 = 11 * x, rb = area_bin(n11, w.inv_gx);
-  const float nA = (float)min((rb + 1) * w.gx - n11, 11), nB = 11.f - nA;
-  double* p = w.s_area + rb * IPPM_AREA_LD + ac.cb;
-  const float v00 = nA * cA, v01 = nA * cB, v10 = nB * cA, v11 = nB * cB;
-  if (v00 != 0.f) atomicAdd(p, (double)v00);                       // ds_add_f64
-  if (v01 != 0.f) atomicAdd(p + 1, (double)v01);
-  if (v10 != 0.f) atomicAdd(p + IPPM_AREA_LD, (double)v10);
-  if (v11 != 0.f) atomicAdd(p + IPPM_AREA_LD + 1, (double)v11);
-}
-// (a workgroup is one wavefront: __syncthreads() is the LDS ordering point between the atomics above and the reads here)
+// The item's contribution to the area sums of its map went into LDS lane-load by lane-load (area_slot, ippm_tiles.h); here it goes out.
+// (a workgroup is one wavefront: __syncthreads() is the LDS ordering point between those atomics and the reads here)
 __device__ __forceinline__ void tile_area_flush(const TileCtx& w, int map_abs) {
   __syncthreads();
   double* dst = w.area + (size_t)map_abs * IPPM_FEAT * IPPM_FEAT;
@@ -93,55 +63,61 @@ struct TileAcc {   // per wavefront, over all its items (all of one env)
   unsigned cells_l, ops_l, cells_g, ops_g;
 };
 
-// One item with at most NA ops (spare slots first) and SLOTS loads in flight per lane.
+// ---- what the two forms of an item (tile_item, tile_item_long) share --------------------------------------------------------------
+struct TileMap {   // the item's map
+  int map_abs;
+  bool is_global;
+  const int32_t* plan;
+  int last_op;
+  __amdgpu_buffer_rsrc_t rmap, rcode;
+};
+__device__ __forceinline__ TileMap tile_item_map(const TileCtx& w, int e, int slot) {
+  TileMap m;
+  m.map_abs = e * (w.n + 1) + slot;
+  m.is_global = slot == w.n;
+  m.plan = w.plan + (size_t)m.map_abs * IPPM_WS_WORDS;
+  m.last_op = m.plan[WS_PLAN + PL_LAST];
+  m.rmap = IPPM_RSRC(m.is_global ? w.global + (size_t)e * IPPM_MAP_PITCH(w.gx, w.gy) : w.local + (size_t)(e * w.n + slot) * IPPM_MAP_PITCH(w.gx, w.gy),
+                     (size_t)w.gx * w.gy * 4);
+  m.rcode = IPPM_RSRC(w.code, (size_t)w.n_envs * w.n * w.TB);
+  return m;
+}
+
+// Record `idx` of the plan: two 16-byte scalar loads (uniform address: the fields stay in SGPRs).
+struct TileOp {
+  int yu, yd;       // columns [yu, yd)
+  int xl, xh;       // (TL) rows [xl, xl + xh)
+  float lm0, lm1;   // log-odds of the two measurement values (0, 0: a clamp-only op)
+  int cs;           // byte of group (row, g) in the source's code tile = (row * row_bytes + g) + cs; a clamp-only op reads some byte of the
+};                  // plane and adds 0 either way
+__device__ __forceinline__ TileOp tile_op_record(const TileCtx& w, const int32_t* plan, int e, int idx) {
+  const int4 a = *reinterpret_cast<const int4*>(plan + WS_OPS + idx * OP_WORDS);       // {type, src, lm0, yu}
+  const int4 b = *reinterpret_cast<const int4*>(plan + WS_OPS + idx * OP_WORDS + 4);   // {yd, xl, xr, lm1}
+  const bool isf = a.x != 0;
+  TileOp o;
+  o.yu = a.w; o.yd = b.x;
+  o.xl = b.y; o.xh = b.z - b.y;
+  o.lm0 = isf ? __int_as_float(a.z) : 0.f;
+  o.lm1 = isf ? __int_as_float(b.w) : 0.f;
+  o.cs = isf ? (e * w.n + a.y) * w.TB - b.y * w.row_bytes - (a.w >> 2) : 0;
+  return o;
+}
+
 // The item is a RUN of `cnt` lane-loads of its region (rows from x0 on, groups [g0, g0 + W)) in row-major order, starting at group
 // `gs` of row x0: lane-load t = q * 64 + lane (t < cnt) is element gs + t of that order.
-// TL (tile storage of the maps, ippm_internal.h): the item is a run of lane-loads of ROWS OF TILES -- x0 a row of tiles, g0 / W / gs lane-loads of it (8 per
-// tile: lane-load G of a row of tiles is row (G >> 1) & 3 of tile G >> 3, cells 4 (G & 1) .. + 3 of that row) -- so consecutive lanes cover whole lines.  A row of
-// tiles holds 4 map rows: whether an op meets a lane's ROW is then a per-lane question as well (the slabs are cut at rows of tiles).
-template <int NA, int SLOTS, bool MIS, bool TRACK, bool TL>
-__device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e, int slot, int x0, int cnt, int gs, int g0, int W, unsigned active) {
-  const int map_abs = e * (w.n + 1) + slot;
-  const bool is_global = slot == w.n;
-  const int32_t* plan = w.plan + (size_t)map_abs * IPPM_WS_WORDS;
-  const int last_op = plan[WS_PLAN + PL_LAST];
-  const __amdgpu_buffer_rsrc_t rmap =
-      IPPM_T_RSRC(is_global ? w.global + (size_t)e * IPPM_MAP_PITCH(w.gx, w.gy) : w.local + (size_t)(e * w.n + slot) * IPPM_MAP_PITCH(w.gx, w.gy),
-                  (size_t)w.gx * w.gy * 4);
-  const __amdgpu_buffer_rsrc_t rcode = IPPM_T_RSRC(w.code, (size_t)w.n_envs * w.n * w.TB);
-  // ---- trip 2a: the op records of the mask.  Spare slots come FIRST: an empty slot still clips, like every op of the reference
-  // -- a no-op ahead of the first real op, but behind the last it would clip that op's unclamped outputs.
-  // Uniform addresses, scalar loads: the fields stay in SGPRs (NA <= 6; items met by more ops: tile_item_long).
-  static_assert(NA <= 6, "straight-line chains are compiled for up to six ops");
-  const int pad = NA - __popc(active);
-  int s_yu[NA], s_yd[NA], cs[NA], s_xl[NA], s_xh[NA];
-  float s_lm0[NA], s_lm1[NA];
-  int keep_slot = -1;
-  {
-    unsigned rem = active;
-#pragma unroll
-    for (int k = 0; k < NA; ++k) {
-      if (k < pad) { s_yu[k] = 0; s_yd[k] = 0; cs[k] = 0; s_lm0[k] = 0.f; s_lm1[k] = 0.f; s_xl[k] = 0; s_xh[k] = 0; continue; }
-      const int idx = __ffs(rem) - 1;
-      rem &= rem - 1u;
-      const int4 a = *reinterpret_cast<const int4*>(plan + WS_OPS + idx * OP_WORDS);       // {type, src, lm0, yu}
-      const int4 b = *reinterpret_cast<const int4*>(plan + WS_OPS + idx * OP_WORDS + 4);   // {yd, xl, xr, lm1}
-      const bool isf = a.x != 0;
-      s_yu[k] = a.w; s_yd[k] = b.x;
-      s_xl[k] = b.y; s_xh[k] = b.z - b.y;      // (TL) the op's rows [xl, xl + xh)
-      s_lm0[k] = isf ? __int_as_float(a.z) : 0.f;
-      s_lm1[k] = isf ? __int_as_float(b.w) : 0.f;
-      // byte of group (row, g) in the source's code tile = (row * row_bytes + g) + cs; a clamp-only op reads some byte of the
-      // plane and adds 0 either way
-      cs[k] = isf ? (e * w.n + a.y) * w.TB - b.y * w.row_bytes - (a.w >> 2) : 0;
-      keep_slot = idx == last_op ? k : keep_slot;
-    }
-  }
-  // ---- trip 2b: every map cell of the item.  Lane-load t = q * 64 + lane -> element tt = gs + t of the region's row-major order
-  // -> (row tt / W, group tt % W); tt < 512, W <= 256: floor(tt / W) = (int)((tt + 0.5) * (1 / W)) exactly (ippm_div_small).
+// TL (tile storage of the maps, ippm_internal.h): the item is a run of lane-loads of ROWS OF TILES -- x0 a row of tiles, g0 / W / gs lane-loads of it
+// (ippm_tile_lane_load) -- so consecutive lanes cover whole lines.  A row of tiles holds 4 map rows: whether an op meets a lane's ROW is then a per-lane
+// question as well (the slabs are cut at rows of tiles).
+template <int SLOTS>
+struct TileCells {
+  CellVec<4> mv[SLOTS];                                  // the cells as loaded
+  int off[SLOTS], coff[SLOTS], ycol[SLOTS], xrow[SLOTS];   // byte offset in the map, row * row_bytes + group, first column (IPPM_T_FAR: none), row
+};
+// trip 2b: every map cell of the item.  Lane-load t = q * 64 + lane -> element tt = gs + t of the region's row-major order
+// -> (row tt / W, group tt % W); tt < 512, W <= 256: floor(tt / W) = (int)((tt + 0.5) * (1 / W)) exactly (ippm_div_small).
+template <int SLOTS, bool TL>
+__device__ __forceinline__ void tile_item_cells(const TileCtx& w, __amdgpu_buffer_rsrc_t rmap, int x0, int cnt, int gs, int g0, int W, TileCells<SLOTS>& c) {
   const float inv_w = __builtin_amdgcn_rcpf((float)W);
-  CellVec<4> mv[SLOTS];
-  int off[SLOTS], coff[SLOTS], ycol[SLOTS], xrow[SLOTS];
 #pragma unroll
   for (int q = 0; q < SLOTS; ++q) {
     const int t = q * 64 + w.lane;
@@ -150,26 +126,73 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
     const bool valid = t < cnt;
     int row, g;
     if (TL) {
-      const int G = g0 + gi;                       // lane-load of the row of tiles x0 + r
-      row = ((x0 + r) << 2) + ((G >> 1) & 3);
-      g = ((G >> 3) << 1) + (G & 1);
-      off[q] = valid ? ((x0 + r) * w.gy + G) * 16 : IPPM_T_OOB;
+      const ippm_lane_load ll = ippm_tile_lane_load(x0 + r, g0 + gi, w.gy);
+      row = ll.row; g = ll.col >> 2;
+      c.off[q] = valid ? ll.off : IPPM_OOB;
     } else {
       row = x0 + r; g = g0 + gi;
-      off[q] = valid ? (row * w.gy + g * 4) * 4 : IPPM_T_OOB;
+      c.off[q] = valid ? (row * w.gy + g * 4) * 4 : IPPM_OOB;
     }
-    xrow[q] = row;
-    coff[q] = row * w.row_bytes + g;
-    ycol[q] = valid ? g * 4 : IPPM_T_FAR;
-    const ippm_t_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rmap, off[q], 0, 0);
-    mv[q].v[0] = __uint_as_float(v.x); mv[q].v[1] = __uint_as_float(v.y); mv[q].v[2] = __uint_as_float(v.z); mv[q].v[3] = __uint_as_float(v.w);
+    c.xrow[q] = row;
+    c.coff[q] = row * w.row_bytes + g;
+    c.ycol[q] = valid ? g * 4 : IPPM_T_FAR;
+    c.mv[q] = buf_load_cells<4>(rmap, c.off[q]);
   }
+}
+// cells y .. y+3 of a lane's group inside the op's columns [yu, yd): bits [lo, hi) -- and (TL) its row inside the op's rows
+template <bool TL>
+__device__ __forceinline__ unsigned tile_op_cells(int yu, int yd, int xl, int xh, int ycol, int xrow) {
+  const int lo = min(max(yu - ycol, 0), 4), hi = min(max(yd - ycol, 0), 4);
+  const unsigned cm = ((1u << (hi - lo)) - 1u) << lo;
+  return !TL || (unsigned)(xrow - xl) < (unsigned)xh ? cm : 0u;
+}
+// One slot's cells go out: the store and the area sums.  (The reward terms of the global map follow in the item's own body, written out in both
+// forms: as a helper of any wording they cost k_fuse_tiles<false, false> 5 spilled registers or <false, true> 101 registers for 90.)
+template <int SLOTS, bool MIS, bool TRACK>
+__device__ __forceinline__ void tile_slot_out(const TileCtx& w, const TileMap& m, const TileCells<SLOTS>& c, int q, const CellVec<4>& out) {
+  // a lane-load past the item's end was never in range; a group no op touches cannot occur inside an interval
+  buf_store_cells_tail<4, MIS>(m.rmap, c.off[q], c.ycol[q], w.gy, out);
+  if (TRACK) area_slot<MIS>(w.gx, w.gy, w.inv_gx, w.inv_gy, w.s_area, c.xrow[q], c.ycol[q] == IPPM_T_FAR ? 0 : c.ycol[q], c.mv[q].v, out.v);
+}
+// the item's flag (some stored cell lies outside the clip range), its area sums, its work counters
+template <bool TRACK>
+__device__ __forceinline__ void tile_item_end(const TileCtx& w, const TileMap& m, TileAcc& acc, float amax, unsigned cells, unsigned opcells) {
+  if (__any(amax > w.lc) && w.lane == 0) w.ws[(size_t)m.map_abs * IPPM_WS_WORDS + WS_FLAG_A] = 1;
+  if (TRACK) tile_area_flush(w, m.map_abs);
+  if (m.is_global) { acc.cells_g += cells; acc.ops_g += opcells; }
+  else { acc.cells_l += cells; acc.ops_l += opcells; }
+}
+
+// One item with at most NA ops (spare slots first) and SLOTS loads in flight per lane.
+template <int NA, int SLOTS, bool MIS, bool TRACK, bool TL>
+__device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e, int slot, int x0, int cnt, int gs, int g0, int W, unsigned active) {
+  const TileMap m = tile_item_map(w, e, slot);
+  // ---- trip 2a: the op records of the mask.  Spare slots come FIRST: an empty slot still clips, like every op of the reference
+  // -- a no-op ahead of the first real op, but behind the last it would clip that op's unclamped outputs.
+  // (NA <= 6; items met by more ops: tile_item_long)
+  static_assert(NA <= 6, "straight-line chains are compiled for up to six ops");
+  const int pad = NA - __popc(active);
+  TileOp op[NA];
+  int keep_slot = -1;
+  {
+    unsigned rem = active;
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+      if (k < pad) { op[k] = TileOp{0, 0, 0, 0, 0.f, 0.f, 0}; continue; }
+      const int idx = __ffs(rem) - 1;
+      rem &= rem - 1u;
+      op[k] = tile_op_record(w, m.plan, e, idx);
+      keep_slot = idx == m.last_op ? k : keep_slot;
+    }
+  }
+  TileCells<SLOTS> c;
+  tile_item_cells<SLOTS, TL>(w, m.rmap, x0, cnt, gs, g0, W, c);
   // ---- trip 3: one measurement-code byte per (slot, op)
   uint32_t cw[SLOTS][NA];
 #pragma unroll
   for (int q = 0; q < SLOTS; ++q)
 #pragma unroll
-    for (int k = 0; k < NA; ++k) cw[q][k] = __builtin_amdgcn_raw_buffer_load_b8(rcode, coff[q] + cs[k], 0, 0);
+    for (int k = 0; k < NA; ++k) cw[q][k] = __builtin_amdgcn_raw_buffer_load_b8(m.rcode, c.coff[q] + op[k].cs, 0, 0);
   // ---- the ordered clamp/add chain (mappings.py:80-124 in log-odds): every op clips its input over the whole grid
   // (mappings.py:110-111), then adds the measurement's log-odds inside its footprint; the outputs of the plan's last op stay
   // unclamped (its rectangle is remembered as possibly out of range), every other cell was clipped again by a later op.
@@ -179,16 +202,12 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
   for (int q = 0; q < SLOTS; ++q) {
     float L[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) L[j] = mv[q].v[j];
+    for (int j = 0; j < 4; ++j) L[j] = c.mv[q].v[j];
     unsigned touched = 0, keepm = 0;
 #pragma unroll
     for (int k = 0; k < NA; ++k) {
-      const int yu = s_yu[k], yd = s_yd[k];
-      const float lm0 = s_lm0[k], lm1 = s_lm1[k];
-      // cells y .. y+3 of my group inside [yu, yd): bits [lo, hi)
-      const int lo = min(max(yu - ycol[q], 0), 4), hi = min(max(yd - ycol[q], 0), 4);
-      unsigned cm = ((1u << (hi - lo)) - 1u) << lo;
-      if (TL) cm = (unsigned)(xrow[q] - s_xl[k]) < (unsigned)s_xh[k] ? cm : 0u;   // ... and my row inside the op's rows
+      const float lm0 = op[k].lm0, lm1 = op[k].lm1;
+      const unsigned cm = tile_op_cells<TL>(op[k].yu, op[k].yd, op[k].xl, op[k].xh, c.ycol[q], c.xrow[q]);
       touched |= cm;
       keepm = k == keep_slot ? cm : keepm;
       opcells += (lm0 != 0.f || lm1 != 0.f) ? __popc(cm) : 0;
@@ -200,33 +219,17 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
       }
     }
     cells += __popc(touched);
-    float out[4];
+    CellVec<4> out;
     if (keep_slot >= 0) {   // (uniform) the item meets the plan's last op: its cells keep their unclamped outputs
 #pragma unroll
-      for (int j = 0; j < 4; ++j) out[j] = ippm_blend(ippm_bitmask(keepm, j), L[j], ippm_clampl(L[j], w.lc));
-      amax = fmaxf(amax, fmaxf(fmaxf(fabsf(out[0]), fabsf(out[1])), fmaxf(fabsf(out[2]), fabsf(out[3]))));
+      for (int j = 0; j < 4; ++j) out.v[j] = ippm_blend(ippm_bitmask(keepm, j), L[j], ippm_clampl(L[j], w.lc));
+      amax = fmaxf(amax, fmaxf(fmaxf(fabsf(out.v[0]), fabsf(out.v[1])), fmaxf(fabsf(out.v[2]), fabsf(out.v[3]))));
     } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) out[j] = ippm_clampl(L[j], w.lc);   // |out| <= lc: nothing to remember
+      for (int j = 0; j < 4; ++j) out.v[j] = ippm_clampl(L[j], w.lc);   // |out| <= lc: nothing to remember
     }
-    {
-      ippm_t_u4 v;
-      v.x = __float_as_uint(out[0]); v.y = __float_as_uint(out[1]); v.z = __float_as_uint(out[2]); v.w = __float_as_uint(out[3]);
-      // a lane-load past the item's end was never in range; a group no op touches cannot occur inside an interval
-      if (MIS) {
-        // (compile-time) rows are not a multiple of 4 wide: the last group of a row hangs over into the next row -- its cells go out
-        // one by one, another lane owns the rest
-        const bool tail = ycol[q] + 4 > w.gy;
-        __builtin_amdgcn_raw_buffer_store_b128(v, rmap, tail ? IPPM_T_OOB : off[q], 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(v.x, rmap, tail ? off[q] : IPPM_T_OOB, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(v.y, rmap, tail && ycol[q] + 1 < w.gy ? off[q] + 4 : IPPM_T_OOB, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(v.z, rmap, tail && ycol[q] + 2 < w.gy ? off[q] + 8 : IPPM_T_OOB, 0, 0);
-      } else {
-        __builtin_amdgcn_raw_buffer_store_b128(v, rmap, off[q], 0, 0);
-      }
-    }
-    if (TRACK) tile_area_slot<MIS>(w, xrow[q], ycol[q] == IPPM_T_FAR ? 0 : ycol[q], mv[q].v, out);
-    if (is_global) {
+    tile_slot_out<SLOTS, MIS, TRACK>(w, m, c, q, out);
+    if (m.is_global) {
       // information-gain terms (utils/reward.py:68-82) of the cells the step changed; an untouched cell contributes exact zeros
       // (same weight, same entropy).  Slots whose touched cells all have weight 0 before and after (believed free, still
       // believed free) skip the entropies: wave-uniform on spatially coherent terrain.
@@ -234,15 +237,15 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const uint32_t tm = ippm_bitmask(touched, j);
-        wa[j] = ippm_masked(tm, ippm_weight_l(out[j], w.wt));
-        wb[j] = ippm_masked(tm, ippm_weight_l(mv[q].v[j], w.wt));
+        wa[j] = ippm_masked(tm, ippm_weight_l(out.v[j], w.wt));
+        wb[j] = ippm_masked(tm, ippm_weight_l(c.mv[q].v[j], w.wt));
         wsum += wa[j] + wb[j];
       }
       if (__any(wsum != 0.f)) {
         float s1 = 0.f, sD = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float hb = ippm_entropy_l(mv[q].v[j], w.lc), ha = ippm_entropy_l(out[j], w.lc);
+          const float hb = ippm_entropy_l(c.mv[q].v[j], w.lc), ha = ippm_entropy_l(out.v[j], w.lc);
           s1 += wa[j] * (hb - ha);
           sD += (wa[j] - wb[j]) * hb;
         }
@@ -251,10 +254,7 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
       }
     }
   }
-  if (__any(amax > w.lc) && w.lane == 0) w.ws[(size_t)map_abs * IPPM_WS_WORDS + WS_FLAG_A] = 1;
-  if (TRACK) tile_area_flush(w, map_abs);
-  if (is_global) { acc.cells_g += cells; acc.ops_g += opcells; }
-  else { acc.cells_l += cells; acc.ops_l += opcells; }
+  tile_item_end<TRACK>(w, m, acc, amax, cells, opcells);
 }
 
 // An item met by MORE than six ops (4 % of the lane-loads at config 5's shape, 0.1 % at config 4's): the same run of lane-loads,
@@ -266,83 +266,45 @@ __device__ __forceinline__ void tile_item(const TileCtx& w, TileAcc& acc, int e,
 template <bool MIS, bool TRACK, bool TL>
 __device__ __forceinline__ void tile_item_long(const TileCtx& w, TileAcc& acc, int e, int slot, int x0, int cnt, int gs, int g0, int W, unsigned active) {
   constexpr int SLOTS = 2;
-  const int map_abs = e * (w.n + 1) + slot;
-  const bool is_global = slot == w.n;
-  const int32_t* plan = w.plan + (size_t)map_abs * IPPM_WS_WORDS;
-  const int last_op = plan[WS_PLAN + PL_LAST];
-  const __amdgpu_buffer_rsrc_t rmap =
-      IPPM_T_RSRC(is_global ? w.global + (size_t)e * IPPM_MAP_PITCH(w.gx, w.gy) : w.local + (size_t)(e * w.n + slot) * IPPM_MAP_PITCH(w.gx, w.gy),
-                  (size_t)w.gx * w.gy * 4);
-  const __amdgpu_buffer_rsrc_t rcode = IPPM_T_RSRC(w.code, (size_t)w.n_envs * w.n * w.TB);
-  const float inv_w = __builtin_amdgcn_rcpf((float)W);
-  CellVec<4> mv[SLOTS];
+  const TileMap m = tile_item_map(w, e, slot);
+  TileCells<SLOTS> c;
+  tile_item_cells<SLOTS, TL>(w, m.rmap, x0, cnt, gs, g0, W, c);
   float L[SLOTS][4];
-  int off[SLOTS], coff[SLOTS], ycol[SLOTS], xrow[SLOTS];
   unsigned touched[SLOTS], keepm[SLOTS];
 #pragma unroll
-  for (int q = 0; q < SLOTS; ++q) {
-    const int t = q * 64 + w.lane;
-    const int r = ippm_div_small(gs + t, inv_w);
-    const int gi = gs + t - r * W;
-    const bool valid = t < cnt;
-    int row, g;
-    if (TL) {
-      const int G = g0 + gi;
-      row = ((x0 + r) << 2) + ((G >> 1) & 3);
-      g = ((G >> 3) << 1) + (G & 1);
-      off[q] = valid ? ((x0 + r) * w.gy + G) * 16 : IPPM_T_OOB;
-    } else {
-      row = x0 + r; g = g0 + gi;
-      off[q] = valid ? (row * w.gy + g * 4) * 4 : IPPM_T_OOB;
-    }
-    xrow[q] = row;
-    coff[q] = row * w.row_bytes + g;
-    ycol[q] = valid ? g * 4 : IPPM_T_FAR;
-    touched[q] = 0; keepm[q] = 0;
-    const ippm_t_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rmap, off[q], 0, 0);
-    mv[q].v[0] = __uint_as_float(v.x); mv[q].v[1] = __uint_as_float(v.y); mv[q].v[2] = __uint_as_float(v.z); mv[q].v[3] = __uint_as_float(v.w);
-  }
-  // one op: its record (two 16-byte scalar loads) and its code byte per slot
-  struct OpIn { int idx, yu, yd, xl, xh; float lm0, lm1; uint32_t cw[SLOTS]; };
+  for (int q = 0; q < SLOTS; ++q) { touched[q] = 0; keepm[q] = 0; }
+  // one op: its record and its code byte per slot
+  struct OpIn { int idx; TileOp o; uint32_t cw[SLOTS]; };
   unsigned rem = active;
-  auto fetch = [&](OpIn& o) __attribute__((always_inline)) {
-    o.idx = __ffs(rem) - 1;
+  auto fetch = [&](OpIn& in) __attribute__((always_inline)) {
+    in.idx = __ffs(rem) - 1;
     rem &= rem - 1u;
-    const int4 a = *reinterpret_cast<const int4*>(plan + WS_OPS + o.idx * OP_WORDS);       // {type, src, lm0, yu}
-    const int4 b = *reinterpret_cast<const int4*>(plan + WS_OPS + o.idx * OP_WORDS + 4);   // {yd, xl, xr, lm1}
-    const bool isf = a.x != 0;
-    o.yu = a.w; o.yd = b.x;
-    o.xl = b.y; o.xh = b.z - b.y;
-    o.lm0 = isf ? __int_as_float(a.z) : 0.f;
-    o.lm1 = isf ? __int_as_float(b.w) : 0.f;
-    const int cs = isf ? (e * w.n + a.y) * w.TB - b.y * w.row_bytes - (a.w >> 2) : 0;
+    in.o = tile_op_record(w, m.plan, e, in.idx);
 #pragma unroll
-    for (int q = 0; q < SLOTS; ++q) o.cw[q] = __builtin_amdgcn_raw_buffer_load_b8(rcode, coff[q] + cs, 0, 0);
+    for (int q = 0; q < SLOTS; ++q) in.cw[q] = __builtin_amdgcn_raw_buffer_load_b8(m.rcode, c.coff[q] + in.o.cs, 0, 0);
   };
   OpIn cur, nxt;
   fetch(cur);
 #pragma unroll
   for (int q = 0; q < SLOTS; ++q)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) L[q][j] = mv[q].v[j];
+    for (int j = 0; j < 4; ++j) L[q][j] = c.mv[q].v[j];
   unsigned cells = 0, opcells = 0;
   bool keeps = false;
   for (;;) {
     const bool more = rem != 0;
     if (more) fetch(nxt);
-    const bool is_last = cur.idx == last_op;   // (the plan's last op has the highest index: if the item meets it, it ends the chain)
+    const bool is_last = cur.idx == m.last_op;   // (the plan's last op has the highest index: if the item meets it, it ends the chain)
     keeps = keeps || is_last;
 #pragma unroll
     for (int q = 0; q < SLOTS; ++q) {
-      const int lo = min(max(cur.yu - ycol[q], 0), 4), hi = min(max(cur.yd - ycol[q], 0), 4);
-      unsigned cm = ((1u << (hi - lo)) - 1u) << lo;
-      if (TL) cm = (unsigned)(xrow[q] - cur.xl) < (unsigned)cur.xh ? cm : 0u;
+      const unsigned cm = tile_op_cells<TL>(cur.o.yu, cur.o.yd, cur.o.xl, cur.o.xh, c.ycol[q], c.xrow[q]);
       touched[q] |= cm;
       keepm[q] = is_last ? cm : keepm[q];
-      opcells += (cur.lm0 != 0.f || cur.lm1 != 0.f) ? __popc(cm) : 0;
+      opcells += (cur.o.lm0 != 0.f || cur.o.lm1 != 0.f) ? __popc(cm) : 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float lm = ippm_masked(ippm_bitmask(cm, j), ippm_blend(ippm_bitmask(cur.cw[q], j), cur.lm1, cur.lm0));
+        const float lm = ippm_masked(ippm_bitmask(cm, j), ippm_blend(ippm_bitmask(cur.cw[q], j), cur.o.lm1, cur.o.lm0));
         L[q][j] = ippm_clampl(L[q][j], w.lc) + lm;
       }
     }
@@ -353,38 +315,25 @@ __device__ __forceinline__ void tile_item_long(const TileCtx& w, TileAcc& acc, i
 #pragma unroll
   for (int q = 0; q < SLOTS; ++q) {
     cells += __popc(touched[q]);
-    float out[4];
+    CellVec<4> out;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) out[j] = ippm_blend(ippm_bitmask(keeps ? keepm[q] : 0u, j), L[q][j], ippm_clampl(L[q][j], w.lc));
-    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(out[0]), fabsf(out[1])), fmaxf(fabsf(out[2]), fabsf(out[3]))));
-    {
-      ippm_t_u4 v;
-      v.x = __float_as_uint(out[0]); v.y = __float_as_uint(out[1]); v.z = __float_as_uint(out[2]); v.w = __float_as_uint(out[3]);
-      if (MIS) {
-        const bool tail = ycol[q] + 4 > w.gy;
-        __builtin_amdgcn_raw_buffer_store_b128(v, rmap, tail ? IPPM_T_OOB : off[q], 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(v.x, rmap, tail ? off[q] : IPPM_T_OOB, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(v.y, rmap, tail && ycol[q] + 1 < w.gy ? off[q] + 4 : IPPM_T_OOB, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(v.z, rmap, tail && ycol[q] + 2 < w.gy ? off[q] + 8 : IPPM_T_OOB, 0, 0);
-      } else {
-        __builtin_amdgcn_raw_buffer_store_b128(v, rmap, off[q], 0, 0);
-      }
-    }
-    if (TRACK) tile_area_slot<MIS>(w, xrow[q], ycol[q] == IPPM_T_FAR ? 0 : ycol[q], mv[q].v, out);
-    if (is_global) {   // the reward terms, as in tile_item
+    for (int j = 0; j < 4; ++j) out.v[j] = ippm_blend(ippm_bitmask(keeps ? keepm[q] : 0u, j), L[q][j], ippm_clampl(L[q][j], w.lc));
+    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(out.v[0]), fabsf(out.v[1])), fmaxf(fabsf(out.v[2]), fabsf(out.v[3]))));
+    tile_slot_out<SLOTS, MIS, TRACK>(w, m, c, q, out);
+    if (m.is_global) {   // the reward terms, as in tile_item
       float wa[4], wb[4], wsum = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const uint32_t tm = ippm_bitmask(touched[q], j);
-        wa[j] = ippm_masked(tm, ippm_weight_l(out[j], w.wt));
-        wb[j] = ippm_masked(tm, ippm_weight_l(mv[q].v[j], w.wt));
+        wa[j] = ippm_masked(tm, ippm_weight_l(out.v[j], w.wt));
+        wb[j] = ippm_masked(tm, ippm_weight_l(c.mv[q].v[j], w.wt));
         wsum += wa[j] + wb[j];
       }
       if (__any(wsum != 0.f)) {
         float s1 = 0.f, sD = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float hb = ippm_entropy_l(mv[q].v[j], w.lc), ha = ippm_entropy_l(out[j], w.lc);
+          const float hb = ippm_entropy_l(c.mv[q].v[j], w.lc), ha = ippm_entropy_l(out.v[j], w.lc);
           s1 += wa[j] * (hb - ha);
           sD += (wa[j] - wb[j]) * hb;
         }
@@ -393,10 +342,7 @@ __device__ __forceinline__ void tile_item_long(const TileCtx& w, TileAcc& acc, i
       }
     }
   }
-  if (__any(amax > w.lc) && w.lane == 0) w.ws[(size_t)map_abs * IPPM_WS_WORDS + WS_FLAG_A] = 1;
-  if (TRACK) tile_area_flush(w, map_abs);
-  if (is_global) { acc.cells_g += cells; acc.ops_g += opcells; }
-  else { acc.cells_l += cells; acc.ops_l += opcells; }
+  tile_item_end<TRACK>(w, m, acc, amax, cells, opcells);
 }
 
 // Workgroup = one wavefront; the grid is (envs, wavefronts per env): wavefront `first` = blockIdx.y of an env takes items first,

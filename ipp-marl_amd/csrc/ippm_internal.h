@@ -138,6 +138,16 @@ int ippm_check_hip(hipError_t err, const char* what);
 __host__ __device__ __forceinline__ int ippm_cell_index(int x, int y, int gy, int tl) {
   return tl ? ((x >> 2) * gy << 2) + ((y >> 3) << 5) + ((x & 3) << 3) + (y & 7) : x * gy + y;
 }
+// The same layout seen from the kernels that walk tile storage in 16-byte LANE-LOADS, 8 per tile, gy per row of tiles: lane-load G
+// of row of tiles R is row (G >> 1) & 3 of tile G >> 3, cells 4 (G & 1) .. + 3 of that row, at byte 16 (R gy + G) of the map -- 8 consecutive
+// lane-loads are one 128-byte line.
+struct ippm_lane_load {
+  int row, col;   // map row and first column of the four cells
+  int off;        // byte offset inside the map
+};
+__host__ __device__ __forceinline__ ippm_lane_load ippm_tile_lane_load(int R, int G, int gy) {
+  return {(R << 2) + ((G >> 1) & 3), ((G >> 3) << 3) + ((G & 1) << 2), (R * gy + G) * 16};
+}
 // the (row-major) linear cell number x * gy + y of the cell stored at float index i of a map
 __host__ __device__ __forceinline__ size_t ippm_stored_cell(size_t i, int gy, int tl) {
   if (!tl) return i;

@@ -87,6 +87,55 @@ __device__ __forceinline__ void store_cells_row(float* rowp, int y, int gy, cons
   for (int q = 0; q < VEC; ++q)
     if (y + q < gy) rowp[y + q] = r.v[q];
 }
+
+// ---- a lane's cell group through a raw buffer resource ------------------------------------------------------------
+typedef unsigned ippm_u4 __attribute__((ext_vector_type(4)));
+// raw buffer resources (gfx9 family descriptor word 3 = 0x00020000): uniform base + per-lane 32-bit byte offset, one VALU
+// per address instead of a 64-bit multiply-add chain, and loads past the end return 0 instead of faulting
+#define IPPM_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
+#define IPPM_OOB 0x7FFFFFF0   // byte offset of a lane without work: past every resource's end -- loads return 0, stores are dropped
+
+// field of lane `lane` (uniform) of a table kept one entry per lane: v_readlane, dynamic indexing at one instruction per field
+__device__ __forceinline__ int lane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+__device__ __forceinline__ float lane_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
+
+template <int VEC>
+__device__ __forceinline__ CellVec<VEC> buf_load_cells(__amdgpu_buffer_rsrc_t r, int off) {
+  CellVec<VEC> c;
+  if (VEC == 4) {
+    const ippm_u4 t = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+    c.v[0] = __uint_as_float(t.x); c.v[1 % VEC] = __uint_as_float(t.y); c.v[2 % VEC] = __uint_as_float(t.z); c.v[3 % VEC] = __uint_as_float(t.w);
+  } else {
+    c.v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
+  }
+  return c;
+}
+// POLICY: the instruction's cache-policy bits (2: non-temporal)
+template <int VEC, int POLICY = 0>
+__device__ __forceinline__ void buf_store_cells(__amdgpu_buffer_rsrc_t r, int off, const CellVec<VEC>& c) {
+  if (VEC == 4) {
+    ippm_u4 t;
+    t.x = __float_as_uint(c.v[0]); t.y = __float_as_uint(c.v[1 % VEC]); t.z = __float_as_uint(c.v[2 % VEC]); t.w = __float_as_uint(c.v[3 % VEC]);
+    __builtin_amdgcn_raw_buffer_store_b128(t, r, off, 0, POLICY);
+  } else {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c.v[0]), r, off, 0, POLICY);
+  }
+}
+// The group at columns y .. y + 3 of a row, without a branch.  MIS (rows are not a multiple of 4 wide): the last group of a row hangs
+// over into the next row -- its cells go out one by one, another lane owns the rest; each store points out of range when not wanted.
+template <int VEC, bool MIS>
+__device__ __forceinline__ void buf_store_cells_tail(__amdgpu_buffer_rsrc_t r, int off, int y, int gy, const CellVec<VEC>& c) {
+  if (VEC == 4 && MIS) {
+    const bool tail = y + 4 > gy;
+    buf_store_cells<VEC>(r, tail ? IPPM_OOB : off, c);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c.v[0]), r, tail ? off : IPPM_OOB, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c.v[1 % VEC]), r, tail && y + 1 < gy ? off + 4 : IPPM_OOB, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(c.v[2 % VEC]), r, tail && y + 2 < gy ? off + 8 : IPPM_OOB, 0, 0);
+  } else {
+    buf_store_cells<VEC>(r, off, c);
+  }
+}
+
 // The four flip decisions of a group of cells lin..lin+3 (any alignment) from the Philox words of counter lin >> 2 and, when the
 // group straddles it, lin >> 2 + 1: word k of counter c belongs to cell 4 c + k (oracle/ipp_oracle.py::philox_correctness).
 __device__ __forceinline__ uint32_t philox_flip_bits4(uint32_t lin, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -208,6 +257,34 @@ __device__ __forceinline__ void area_row(AreaAcc& acc, double* s_area, const Are
 #pragma unroll
   for (int q = 0; q < VEC; ++q) { sd += d[q]; cA += ac.wA[q] * d[q]; }
   acc.add(s_area, ac.cb, x, gx, inv_gx, cA, 11.f * sd - cA);
+}
+// The same for ONE lane-load at (row x, columns y .. y + 3) of a kernel whose lanes do not walk down rows (K3's and the tile fusion's
+// one-trip forms): the weighted sigmoid differences d[0..3] of its four cells straight into the (at most) 2 x 2 bins the group meets.
+__device__ __forceinline__ void area_slot_add(int gx, int gy, float inv_gx, float inv_gy, double* s_area, int x, int y, const float* d) {
+  float sd = 0.f, cA = 0.f;
+  const AreaCols<4> ac = area_cols<4>(y, gy, inv_gy);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { sd += d[j]; cA += ac.wA[j] * d[j]; }
+  const float cB = 11.f * sd - cA;
+  const int n11 = 11 * x, rb = area_bin(n11, inv_gx);
+  const float nA = (float)min((rb + 1) * gx - n11, 11), nB = 11.f - nA;
+  double* p = s_area + rb * IPPM_AREA_LD + ac.cb;
+  const float v00 = nA * cA, v01 = nA * cB, v10 = nB * cA, v11 = nB * cB;
+  if (v00 != 0.f) atomicAdd(p, (double)v00);                       // ds_add_f64
+  if (v01 != 0.f) atomicAdd(p + 1, (double)v01);
+  if (v10 != 0.f) atomicAdd(p + IPPM_AREA_LD, (double)v10);
+  if (v11 != 0.f) atomicAdd(p + IPPM_AREA_LD + 1, (double)v11);
+}
+// ... from the cells as loaded (`old4`) and as stored (`new4`; a lane-load that loaded zeros and stores nothing: zero difference).
+// MIS (rows not a multiple of 4 wide): the cells of a row's last group that hang over into the next row were loaded and run through
+// the chain but are never stored (another lane owns them): they contribute nothing here either.
+template <bool MIS>
+__device__ __forceinline__ void area_slot(int gx, int gy, float inv_gx, float inv_gy, double* s_area, int x, int y, const float* old4,
+                                          const float* new4) {
+  float d[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) d[j] = (MIS && y + j >= gy) ? 0.f : sigmoid_diff(new4[j], old4[j]);
+  area_slot_add(gx, gy, inv_gx, inv_gy, s_area, x, y, d);
 }
 
 #endif  // __HIPCC__

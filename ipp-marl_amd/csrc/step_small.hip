@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "ippm_k1.h"
+#include "ippm_tiles.h"
 
 // ======================================================================================================
 // comm matrix
@@ -237,8 +238,6 @@ __global__ void k_plan(const ippm_config* __restrict__ c, const int32_t* __restr
 // Wave-cooperative per map: lane l ranks edge l (rank sort + one ds_permute, as the row walker did per item), lane s then owns
 // slab s and merges the intervals of the ops sorted by their first column; finished intervals go out as the walk proceeds.
 // ======================================================================================================
-__device__ __forceinline__ int tb_lane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
 // The items of one REGION = rows [xa, xb) x groups [g0, g1) of a (slab, interval), met by the ops of `mask` (all arguments
 // wave-uniform; every lane takes part).  The region's lane-loads in row-major order, t = (row - xa) * W + (group - g0), are cut
 // into runs of 64 * slots: item i is the run [i * cap, i * cap + count) -- it starts wherever in a row the previous one ended, so
@@ -308,11 +307,11 @@ __device__ __forceinline__ void tile_build_map(const int4* s_ops, int nops, int 
   }
   int rank = 0, orank = 0;
   for (int j = 0; j < n_edges; ++j) {
-    const int ej = tb_lane_i(edge, j);
+    const int ej = lane_i(edge, j);
     rank += (ej < edge || (ej == edge && j < lane)) ? 1 : 0;
   }
   for (int j = 0; j < nops; ++j) {
-    const int yj = tb_lane_i(r_yu, j);
+    const int yj = lane_i(r_yu, j);
     orank += (yj < r_yu || (yj == r_yu && j < lane)) ? 1 : 0;
   }
   const int sorted = __builtin_amdgcn_ds_permute((lane < n_edges ? rank : lane) << 2, edge);  // lane `rank` receives my edge
@@ -327,8 +326,8 @@ __device__ __forceinline__ void tile_build_map(const int4* s_ops, int nops, int 
     bool in = false, done = mask != 0;
     int lo = 0, hi = 0, o = 0;
     if (r < nops) {
-      o = tb_lane_i(order, r);  // op with the r-th smallest first column
-      const int yu = tb_lane_i(r_yu, o), yd = tb_lane_i(r_yd, o), xl = tb_lane_i(r_xl, o), xr = tb_lane_i(r_xr, o);
+      o = lane_i(order, r);  // op with the r-th smallest first column
+      const int yu = lane_i(r_yu, o), yd = lane_i(r_yd, o), xl = lane_i(r_xl, o), xr = lane_i(r_xr, o);
       in = slab_on && xl <= xa && xa < xr;
       if (tl) { lo = (yu >> 3) << 3; hi = ((yd + 7) >> 3) << 3; }
       else { lo = (yu >> 2) & ~round_mask; hi = min(G, (((yd + 3) >> 2) + round_mask) & ~round_mask); }
@@ -342,8 +341,8 @@ __device__ __forceinline__ void tile_build_map(const int4* s_ops, int nops, int 
     if (done && !big) tile_write_items(items, env_cap, atomicAdd(s_items, n_mine), 0, 1, n_mine, sh, slot, xa, xb, g0, g1, mask);
     for (unsigned long long pend = __ballot(big); pend != 0; pend &= pend - 1) {
       const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)pend) - 1);
-      tile_emit_region(items, env_cap, s_items, slot, tb_lane_i(xa, src), tb_lane_i(xb, src), tb_lane_i(g0, src), tb_lane_i(g1, src),
-                       (unsigned)tb_lane_i((int)mask, src), lane);
+      tile_emit_region(items, env_cap, s_items, slot, lane_i(xa, src), lane_i(xb, src), lane_i(g0, src), lane_i(g1, src),
+                       (unsigned)lane_i((int)mask, src), lane);
     }
     if (done) mask = 0;
     if (in) {

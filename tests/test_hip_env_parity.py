@@ -129,6 +129,57 @@ def test_production_randomness_matches_oracle(name, over, n_envs):
     check_philox_episodes(name, over, n_envs)
 
 
+def _check_env_step(env, e, n, t, rec, comm, glob, local, sensed, reward, obs, state, feats):
+    """Env e of the batch after step t against the oracle's record of that step (``n``: the agents flying in it); ``local`` the locally
+    fused maps before the step or ``sensed`` the local maps after its sensing (the one-launch step), ``feats``: the network inputs too.
+    Returns the number of class-weight threshold ties met (conftest)."""
+    fused_step = local is None
+    ties = 0
+    want_comm = np.zeros((env.d.n_agents, env.d.n_agents), dtype=np.uint8)   # (nobody hears, or is heard by, the others)
+    for i, ks in enumerate(rec["received"]):
+        want_comm[i, ks] = 1
+    assert np.array_equal(comm[e], want_comm), (t, e)
+    assert np.array_equal(env.mask[e, :n].cpu().numpy(), rec["masks"].astype(np.uint8)), (t, e)
+    assert np.array_equal(env.action[e, :n].cpu().numpy(), rec["actions"]), (t, e)
+    assert np.array_equal(env.pos[e, :n].cpu().numpy(), rec["next_positions"]), (t, e)
+    assert np.array_equal(env.rect[e, :n].cpu().numpy(), rec["next_rects"]), (t, e)
+    assert not env.rect[e, n:].any(), (t, e)          # the others publish empty footprints
+    # every cell of every map within 1e-5 -- prior != 0.5 included: there every message shifts every cell of the grid, and the
+    # chain of a fusion runs in float64 registers and is rounded once, at the store
+    strict = True
+    if fused_step:
+        assert_posteriors(sensed[e, :n], np.array(rec["sensed_local"]), strict=strict, msg=f"local after sensing t={t} e={e}")
+    else:
+        assert_posteriors(local[e, :n], np.array(rec["fused_local"]), strict=strict, msg=f"fused local t={t} e={e}")
+    assert_posteriors(glob[e], rec["global_map"], strict=strict, msg=f"global t={t} e={e}")
+    # returns: 1e-5 in every regime.  (Altitudes outside the sensor model's table are noise-free: cells jump between exactly
+    # 0 / 1 and the clip, the reward terms are of size 1 with both signs and S1 is what is left after they cancel -- every
+    # fusion kernel sums a row's / slot's cells in float32 and the lanes in float64; float32 lane sums showed at 2e-4 there.)
+    noise_free = any(z not in (5, 10, 15) for z in env.d.altitudes)
+    rt = RTOL
+    # (the rewards are affine in the sums, 22 S1/S2 - 0.5 and 10 S1/cells - 0.17 (utils/reward.py:37-40): the tolerance of
+    #  the sums applies to the part in front of the offset, which matters when a reward is close to 0)
+    got_r = reward[e].cpu().numpy()
+    np.testing.assert_allclose(got_r[0], rec["relative_reward"], rtol=rt, atol=1e-6 + rt * 0.5)
+    np.testing.assert_allclose(got_r[1], rec["absolute_reward"], rtol=rt, atol=1e-6 + rt * 0.17)
+    # (S1 = sum of w(a) (H(b) - H(a)) is a difference of two sums of the size of S2: its absolute error is a fraction of S2.
+    #  Default: 2e-8 of S2.  Noise-free measurements: the terms are +-1 and nearly cancel, what remains is the float32 entropy
+    #  of the saturated cells themselves, the same 3e-8 on each of them -- measured 5.4e-8 of S2 on an S1 of 0.83 next to an S2
+    #  of 770: 2e-7.  prior != 0.5: every cell of the float32 maps enters both sums at every fusion with the 5e-7 absolute
+    #  rounding of its stored log-odds: 1e-6 of S2.)
+    s_scale = 1e-6 if env.d.prior != 0.5 else (2e-7 if noise_free else 2e-8)
+    np.testing.assert_allclose(env.sums[e, :2].cpu().numpy(), [rec["s1"], rec["s2"]], rtol=rt, atol=1e-6 + s_scale * abs(rec["s2"]))
+    if feats:   # (prior != 0.5: the area sums take a small change of EVERY cell at every fusion: 6e-6 absolute there)
+        fa = 2e-6 if env.d.prior == 0.5 and not noise_free else 6e-6   # (noise-free: float32 increments of size 1/2)
+        got_obs, got_state = obs[e].cpu().numpy(), state[e].cpu().numpy()
+        for i in range(n):   # a differing element must be a proven class-weight threshold tie (conftest)
+            dec = {3: rec["decide_local"][i], 4: rec["decide_fp"][i]}
+            ties += assert_features_or_ties(got_obs[i], rec["observations"][i], dec, RTOL, fa, f"obs t={t} e={e} i={i}")
+            dec[8] = rec["decide_global"]
+            ties += assert_features_or_ties(got_state[i], rec["states"][i], dec, RTOL, fa, f"state t={t} e={e} i={i}")
+    return ties
+
+
 def check_philox_episodes(name, over, n_envs, seed=0x1234567ABC, first_episode=11, track_area=True, fused_step=False, terrain="split",
                           team_sizes=None, map_layout="auto"):
     """The every-step comparison of a batch with the oracle under the production randomness; returns the number of class-weight
@@ -166,50 +217,8 @@ def check_philox_episodes(name, over, n_envs, seed=0x1234567ABC, first_episode=1
         glob = env.posterior_global().cpu().numpy()
         sensed = env.posterior_local().cpu().numpy() if fused_step else None
         for e, (log, _, _) in enumerate(oracles):
-            rec = log[t]
-            n = teams[e]                      # the agents flying in this env (all of them unless team_sizes is given)
-            want_comm = np.zeros((env.d.n_agents, env.d.n_agents), dtype=np.uint8)   # (nobody hears, or is heard by, the others)
-            for i, ks in enumerate(rec["received"]):
-                want_comm[i, ks] = 1
-            assert np.array_equal(comm[e], want_comm), (t, e)
-            assert np.array_equal(env.mask[e, :n].cpu().numpy(), rec["masks"].astype(np.uint8)), (t, e)
-            assert np.array_equal(env.action[e, :n].cpu().numpy(), rec["actions"]), (t, e)
-            assert np.array_equal(env.pos[e, :n].cpu().numpy(), rec["next_positions"]), (t, e)
-            assert np.array_equal(env.rect[e, :n].cpu().numpy(), rec["next_rects"]), (t, e)
-            assert not env.rect[e, n:].any(), (t, e)          # the others publish empty footprints
-            # every cell of every map within 1e-5 -- prior != 0.5 included: there every message shifts every cell of the grid, and the
-            # chain of a fusion runs in float64 registers and is rounded once, at the store
-            strict = True
-            if fused_step:
-                assert_posteriors(sensed[e, :n], np.array(rec["sensed_local"]), strict=strict, msg=f"local after sensing t={t} e={e}")
-            else:
-                assert_posteriors(local[e, :n], np.array(rec["fused_local"]), strict=strict, msg=f"fused local t={t} e={e}")
-            assert_posteriors(glob[e], rec["global_map"], strict=strict, msg=f"global t={t} e={e}")
-            # returns: 1e-5 in every regime.  (Altitudes outside the sensor model's table are noise-free: cells jump between exactly
-            # 0 / 1 and the clip, the reward terms are of size 1 with both signs and S1 is what is left after they cancel -- every
-            # fusion kernel sums a row's / slot's cells in float32 and the lanes in float64; float32 lane sums showed at 2e-4 there.)
-            noise_free = any(z not in (5, 10, 15) for z in env.d.altitudes)
-            rt = RTOL
-            # (the rewards are affine in the sums, 22 S1/S2 - 0.5 and 10 S1/cells - 0.17 (utils/reward.py:37-40): the tolerance of
-            #  the sums applies to the part in front of the offset, which matters when a reward is close to 0)
-            got_r = reward[e].cpu().numpy()
-            np.testing.assert_allclose(got_r[0], rec["relative_reward"], rtol=rt, atol=1e-6 + rt * 0.5)
-            np.testing.assert_allclose(got_r[1], rec["absolute_reward"], rtol=rt, atol=1e-6 + rt * 0.17)
-            # (S1 = sum of w(a) (H(b) - H(a)) is a difference of two sums of the size of S2: its absolute error is a fraction of S2.
-            #  Default: 2e-8 of S2.  Noise-free measurements: the terms are +-1 and nearly cancel, what remains is the float32 entropy
-            #  of the saturated cells themselves, the same 3e-8 on each of them -- measured 5.4e-8 of S2 on an S1 of 0.83 next to an S2
-            #  of 770: 2e-7.  prior != 0.5: every cell of the float32 maps enters both sums at every fusion with the 5e-7 absolute
-            #  rounding of its stored log-odds: 1e-6 of S2.)
-            s_scale = 1e-6 if env.d.prior != 0.5 else (2e-7 if noise_free else 2e-8)
-            np.testing.assert_allclose(env.sums[e, :2].cpu().numpy(), [rec["s1"], rec["s2"]], rtol=rt, atol=1e-6 + s_scale * abs(rec["s2"]))
-            if feats:   # (prior != 0.5: the area sums take a small change of EVERY cell at every fusion: 6e-6 absolute there)
-                fa = 2e-6 if env.d.prior == 0.5 and not noise_free else 6e-6   # (noise-free: float32 increments of size 1/2)
-                got_obs, got_state = obs[e].cpu().numpy(), state[e].cpu().numpy()
-                for i in range(n):   # a differing element must be a proven class-weight threshold tie (conftest)
-                    dec = {3: rec["decide_local"][i], 4: rec["decide_fp"][i]}
-                    ties += assert_features_or_ties(got_obs[i], rec["observations"][i], dec, RTOL, fa, f"obs t={t} e={e} i={i}")
-                    dec[8] = rec["decide_global"]
-                    ties += assert_features_or_ties(got_state[i], rec["states"][i], dec, RTOL, fa, f"state t={t} e={e} i={i}")
+            # (teams[e]: the agents flying in this env -- all of them unless team_sizes is given)
+            ties += _check_env_step(env, e, teams[e], t, log[t], comm, glob, local, sensed, reward, obs, state, feats)
     final = env.posterior_local().cpu().numpy()
     for e, (_, final_local, _) in enumerate(oracles):
         assert_posteriors(final[e, :teams[e]], final_local, strict=True, msg=f"final local e={e}")
@@ -255,6 +264,57 @@ def test_untracked_env_step_matches_oracle(name, over, n_envs, fused_step):
     items from the plan kernel's work list -- through the same every-step comparison with the oracle (maps, masks, actions,
     rewards); ``fused_step`` = ``steps()`` alone, the single-plan-launch sequence of bench.py's timed loop."""
     check_philox_episodes(name, over, n_envs, seed=0x51C0FFEE11, first_episode=23, track_area=False, fused_step=fused_step)
+
+
+# Grids of 46 x 46 and 48 x 48 cells (15 m flight level; 46 is not a multiple of 4 wide, 48 x 48 is whole 4 x 8 tiles), both wide enough
+# for 16-byte lane groups and the tile form of the fusion, with footprints of 16 cells (the network inputs need 11).
+_NINE_OP_GRIDS = {46: dict(sensor__field_of_view__angle_x=60.0, sensor__field_of_view__angle_y=60.0, sensor__pixel__number_x=16, sensor__pixel__number_y=16),
+                  48: dict(sensor__field_of_view__angle_x=60.7, sensor__field_of_view__angle_y=60.7, sensor__pixel__number_x=17, sensor__pixel__number_y=17)}
+
+
+@pytest.mark.parametrize("cells,track_area,map_layout", [(46, False, "rows"), (46, True, "rows"), (48, False, "rows"), (48, True, "rows"),
+                                                         (48, False, "tiles"), (48, True, "tiles")])
+def test_items_met_by_nine_ops_match_oracle(cells, track_area, map_layout):
+    """The tile fusion's run-time op loop (fuse_tiles.hip, tile_item_long: items met by more than six ops) in each of its six
+    instantiations -- rows only 4-byte aligned / area sums tracked / tile storage.  Eight UAVs start on ONE lattice point at one
+    altitude, everyone in range: every local plan and the global plan of step 0 cover one rectangle with nine ops, so every item of the
+    step takes that loop.  Env 0 starts in the middle of the world, env 1 in its far corner, where the footprint ends on the last
+    (46 wide: overhanging) group of the rows.  One step after the reset, against the oracle as check_philox_episodes holds every step."""
+    from ippmarl.vec_env import POLICY_UNIFORM
+    seed, eps = 0x9095, [3, 4]
+    params = make_params("small", experiment__missions__n_agents=8, experiment__uav__communication_range=100,
+                         experiment__constraints__min_altitude=15, experiment__constraints__max_altitude=15, experiment__constraints__num_actions=9,
+                         **_NINE_OP_GRIDS[cells])
+    d = O.Derived(params)
+    assert (d.gx, d.gy, d.n_agents) == (cells, cells, 8)
+    starts = [[[25, 25, 15]] * 8, [[50, 50, 15]] * 8]
+    env = _env(params, 2, philox_seed=seed, track_area=track_area, map_layout=map_layout)
+    assert env.tiled == (map_layout == "tiles")
+    env.reset(eps, start_positions=torch.tensor(starts, dtype=torch.int32))
+    env.profile = True
+    obs = env.build_observations(0, features=track_area)      # (the local and the global fusion of step 0: one launch)
+    env.profile = False
+    local = env.posterior_local().cpu().numpy()
+    reward, _, state = env.steps(0, policy=POLICY_UNIFORM, features=track_area)
+    want = "k_fuse_tiles<%s, %s%s>" % (str(cells % 4 != 0).lower(), str(track_area).lower(), ", true" if env.tiled else "")
+    assert env.event_times_us()["fuse"]["kernel"] == want
+    comm, glob = env.comm.cpu().numpy(), env.posterior_global().cpu().numpy()
+    for e, episode in enumerate(eps):
+        holder = {}
+
+        def correctness(i, s, shape):
+            pos = holder["ep"].agents[i]["position"]
+            _, fc = O.project_field_of_view(d, pos)
+            return O.philox_correctness(seed, episode, i, s, fc, d.gy, O.noise_of_altitude(pos[2]))
+
+        ep = O.OracleEpisode(params, episode, correctness, lambda i, t, mask, o: O.uniform_valid_action(O.philox_action_word(seed, episode, i, t), mask),
+                             comm_draw=lambda i, j, t: O.philox_comm_draw(seed, episode, i, j, t), build_features=True,
+                             start_positions=starts[e], exact=True)
+        holder["ep"] = ep
+        rec = ep.step(0)
+        assert all(len(ks) == 8 for ks in rec["received"]) and len({tuple(r) for r in rec["rects"]}) == 1   # nine ops, one rectangle
+        _check_env_step(env, e, 8, 0, rec, comm, glob, local, None, reward, obs, state, track_area)
+    assert env.counters()["work_list_rejects"] == 0 and int(env.fault.abs().sum()) == 0
 
 
 @pytest.mark.parametrize("name,n_envs", [("c2", 3), ("small", 4)])
