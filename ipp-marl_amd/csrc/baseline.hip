@@ -4,22 +4,7 @@
 // exactly like K3 does (4 grid-aligned cells per lane), accumulates in float64 and is deterministic (no atomics), so
 // candidates with identical cell multisets get bit-identical gains and argmax ties resolve like the reference's.
 
-#include "ippm_internal.h"
-
-__device__ __forceinline__ void ig_action_offset(int A, int a, int s, int& dx, int& dy, int& dz) {
-  dx = dy = dz = 0;
-  if (A == 4) {
-    if (a == 0) dx = -s; else if (a == 1) dy = -s; else if (a == 2) dy = s; else dx = s;
-  } else if (A == 6) {
-    if (a == 0) dz = s; else if (a == 1) dx = -s; else if (a == 2) dy = -s; else if (a == 3) dy = s;
-    else if (a == 4) dx = s; else dz = -s;
-  } else if (A == 9) {
-    dx = (a / 3 - 1) * s; dy = (a % 3 - 1) * s;
-  } else {
-    int layer = a / 9, c9 = a % 9;
-    dz = (1 - layer) * s; dx = (c9 / 3 - 1) * s; dy = (c9 % 3 - 1) * s;
-  }
-}
+#include "ippm_k1.h"   // action_offset: the planner and K1 agree on what action a means
 
 // Expected weighted entropy reduction of one cell with (clipped) belief log-odds l under a measurement of log-odds +-ln
 // (IG_baseline.py:236-268):  p (H(l) - H(l1)) w(l1) + (1 - p) (H(l) - H(l0)) w(l0),  w = the posterior itself inside the weight
@@ -79,7 +64,7 @@ k_ig_candidates(const ippm_config* __restrict__ c, const float* __restrict__ loc
   if (!mask[cand]) { if (threadIdx.x == 0) gains[cand] = 0.f; return; }
   const int32_t* p = pos + (size_t)(e * n + i) * 3;
   int dx, dy, dz;
-  ig_action_offset(A, a, c->spacing, dx, dy, dz);
+  action_offset(A, a, c->spacing, dx, dy, dz);
   int r[4];
   ippm_footprint_rect(c, p[0] + dx, p[1] + dy, p[2] + dz, r, nullptr);
   const int yu = r[0], yd = r[1], xl = r[2], xr = r[3];
@@ -226,7 +211,7 @@ k_ig_select(const ippm_config* __restrict__ c, const int32_t* __restrict__ pos, 
     for (int b = 0; b < A; ++b) total += gains[(size_t)(e * n + i) * A + b];
     rel[q] = gains[(size_t)(e * n + i) * A + a] / total;
     int dx, dy, dz;
-    ig_action_offset(A, a, c->spacing, dx, dy, dz);
+    action_offset(A, a, c->spacing, dx, dy, dz);
     const int32_t* p = pos + (size_t)(e * n + i) * 3;
     cpos[q][0] = p[0] + dx; cpos[q][1] = p[1] + dy; cpos[q][2] = p[2] + dz;
     cmask[q] = mask[(size_t)(e * n + i) * A + a];
@@ -283,8 +268,6 @@ k_f1_counts(const ippm_config* __restrict__ c, const float* __restrict__ maps, c
     atomicAdd(&out[m * 3 + 2], (unsigned long long)d);
   }
 }
-
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 extern "C" int ippm_ig_candidates(ippm_ctx* ctx, const float* local, const int32_t* pos, const uint8_t* mask, float* gains,
                                   int32_t n_envs, void* stream) {

@@ -154,11 +154,11 @@ __global__ void k_footprint(const ippm_config* __restrict__ c, const int32_t* __
 // ======================================================================================================
 // K3: sense + Bayesian update of the agent's own footprint tile
 //   Mapping.update_grid_map = Simulation.get_measurement + apply_update (mappings.py:32-78,109-124; simulations.py:42-65)
-// TRACK: also add the cells' change into the map's 11x11 area sums (ippm_tiles.h).
+// The form for narrow grids (grid_y < 44: no 16-byte lane groups) with tracked area sums: one cell per lane, one row in flight,
+// every cell's change added into the map's 11x11 area sums (ippm_tiles.h).
 // The launch carries ceil(E/256) extra workgroups that complete the reward of the step's global fusion
 // (k_reward_finalize's job: K3 is the kernel that closes an env step, the sums are final when it starts).
 // ======================================================================================================
-template <int VEC, int UNR, bool TRACK>
 __global__ void __launch_bounds__(256)
 k_sense_update(const ippm_config* __restrict__ c, const int64_t* __restrict__ episode,
                const int32_t* __restrict__ pos, const uint8_t* __restrict__ truth, float* __restrict__ local,
@@ -195,7 +195,7 @@ k_sense_update(const ippm_config* __restrict__ c, const int64_t* __restrict__ ep
   const uint32_t thr = c->flip_threshold[k];
   const float lc = c->logit_clip;
   const float lp = c->logit_prior;  // 0 unless mapping.prior != 0.5 (mappings.py:112-116: l_x + l_y - l_p)
-  const RowGeom g = make_geom<VEC>(yu, yd);
+  const RowGeom g = make_geom<1>(yu, yd);
   const int tile_y0 = yu & ~3;
   const int rows_per_wg = (h + split - 1) / split;
   const int r0 = part * rows_per_wg, r1 = min(h, r0 + rows_per_wg);
@@ -203,85 +203,45 @@ k_sense_update(const ippm_config* __restrict__ c, const int64_t* __restrict__ ep
   const int sub = lane >> g.shift, gl = lane & (g.lpr - 1);
   float* map = local + (size_t)(e * n + i) * gx * gy;
   const uint8_t* tr = truth + (size_t)e * ippm_truth_bytes(gx, gy);
-  const size_t TB = ippm_tile_bytes(S, VEC);
+  const size_t TB = ippm_tile_bytes(S, 1);
   uint8_t* cd = code + (size_t)(e * n + i) * TB;
   const uint8_t* fl = flips ? flips + (size_t)(e * n + i) * TB : nullptr;
   const int64_t ep = episode ? episode[e] : 0;
   const uint32_t sw = ippm_stream_word((uint32_t)i, (uint32_t)stage, IPPM_DOMAIN_FLIP);
   const uint32_t k0 = (uint32_t)c->philox_seed, k1 = (uint32_t)(c->philox_seed >> 32);
-  const int stride = 4 * g.rpw;
-  __shared__ double s_area[TRACK ? (IPPM_FEAT + 1) * IPPM_AREA_LD : 1];
-  float inv_gx = 0.f, inv_gy = 0.f;
-  if (TRACK) {
-    area_lds_clear(s_area);
-    inv_gx = __builtin_amdgcn_rcpf((float)gx);
-    inv_gy = __builtin_amdgcn_rcpf((float)gy);
-    __syncthreads();
-  }
+  __shared__ double s_area[(IPPM_FEAT + 1) * IPPM_AREA_LD];
+  area_lds_clear(s_area);
+  const float inv_gx = __builtin_amdgcn_rcpf((float)gx), inv_gy = __builtin_amdgcn_rcpf((float)gy);
+  __syncthreads();
   bool exceed = false;
   for (int gi = gl; gi < g.groups; gi += g.lpr) {
-    const int y = g.y0 + gi * VEC;
-    AreaCols<VEC> ac;
+    const int y = g.y0 + gi;   // (yu <= y < yd: a one-cell group is always inside the footprint)
+    const AreaCols<1> ac = area_cols<1>(y, gy, inv_gy);
     AreaAcc acc;
-    if (TRACK) { ac = area_cols<VEC>(y, gy, inv_gy); acc.init(); }
-    for (int row = r0 + wv * g.rpw + sub; row < r1; row += stride * UNR) {
-      // UNR independent rows per lane: all their loads are in flight before the first use
-      CellVec<VEC> m[UNR];
-      uint32_t tw[UNR], fw[UNR];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const int rr = row + u * stride;
-        tw[u] = 0; fw[u] = 0;
-        if (rr < r1) {
-          const size_t cell = (size_t)(xl + rr) * gy + y;
-          m[u] = load_cells_row<VEC>(map + (size_t)(xl + rr) * gy, y, gy);
-          tw[u] = VEC == 4 ? ippm_truth4(tr, cell, ippm_truth_bytes(gx, gy)) : ippm_truth1(tr, cell);
-          if (fl) fw[u] = load_bits<VEC>(fl, rr, y - tile_y0, S);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const int rr = row + u * stride;
-        if (rr >= r1) continue;
-        const size_t cell = (size_t)(xl + rr) * gy + y;
-        uint32_t phbits = 0;
-        if (!fl && VEC == 4) phbits = philox_flip_bits4((uint32_t)cell, (uint32_t)ep, sw, (uint32_t)(ep >> 32), k0, k1, thr, (gy & 3) != 0);
-        uint32_t cw = 0;
-        float d[VEC];
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) {
-          // branch-free: cells of an edge group that lie outside the footprint keep their value
-          const bool in = (unsigned)(y + q - yu) < (unsigned)w;
-          uint32_t flip;
-          if (fl) flip = (fw[u] >> q) & 1u;
-          else if (VEC == 4) flip = (phbits >> q) & 1u;
-          else {
-            Philox4 p1 = ippm_philox((uint32_t)((cell + q) >> 2), (uint32_t)ep, sw, (uint32_t)(ep >> 32), k0, k1);
-            flip = p1.v[(cell + q) & 3] < thr ? 1u : 0u;
-          }
-          const uint32_t obs = ((tw[u] >> q) & 1u) ^ flip;
-          // mappings.py:109-124 in log-odds: clip the prior belief, add the measurement's log-odds
-          const float old = m[u].v[q];
-          const float l = ippm_clampl(old, lc) + ((obs ? lm1 : lm0) - lp);
-          exceed |= in & (fabsf(l) > lc);
-          m[u].v[q] = in ? l : old;
-          cw |= (in ? obs : 0u) << q;
-          if (TRACK) d[q] = in ? sigmoid_diff(l, old) : 0.f;
-        }
-        store_cells_row<VEC>(map + (size_t)(xl + rr) * gy, y, gy, m[u]);
-        store_bits<VEC>(cd, rr, y - tile_y0, S, cw);
-        if (TRACK) area_row<VEC>(acc, s_area, ac, xl + rr, gx, inv_gx, d);
-      }
+    acc.init();
+    for (int row = r0 + wv * g.rpw + sub; row < r1; row += 4 * g.rpw) {
+      const size_t cell = (size_t)(xl + row) * gy + y;
+      float* rowp = map + (size_t)(xl + row) * gy;
+      const float old = load_cells_row<1>(rowp, y, gy).v[0];
+      const uint32_t tw = ippm_truth1(tr, cell);
+      const uint32_t fw = fl ? load_bits<1>(fl, row, y - tile_y0, S) : 0u;   // (requested with the cell and the truth bit)
+      const uint32_t flip = fl ? fw : (ippm_philox((uint32_t)(cell >> 2), (uint32_t)ep, sw, (uint32_t)(ep >> 32), k0, k1).v[cell & 3] < thr ? 1u : 0u);
+      const uint32_t obs = tw ^ flip;
+      // mappings.py:109-124 in log-odds: clip the prior belief, add the measurement's log-odds
+      const float l = ippm_clampl(old, lc) + ((obs ? lm1 : lm0) - lp);
+      exceed |= fabsf(l) > lc;
+      store_cells_row<1>(rowp, y, gy, CellVec<1>{{l}});
+      store_bits<1>(cd, row, y - tile_y0, S, obs);
+      const float d = sigmoid_diff(l, old);
+      area_row<1>(acc, s_area, ac, xl + row, gx, inv_gx, &d);
     }
-    if (TRACK) acc.flush(s_area, ac.cb);
+    acc.flush(s_area, ac.cb);
   }
   if (ws && __any(exceed) && lane == 0) ws[(size_t)(e * (n + 1) + i) * IPPM_WS_WORDS + WS_FLAG_S] = 1;
   if (counters && part == 0 && threadIdx.x == 0)
     atomicAdd(&counters[(tile & (IPPM_COUNTER_SLOTS - 1)) * 8 + 0], (unsigned long long)h * w);
-  if (TRACK) {
-    __syncthreads();
-    area_lds_commit(s_area, area + (size_t)(e * (n + 1) + i) * IPPM_FEAT * IPPM_FEAT);
-  }
+  __syncthreads();
+  area_lds_commit(s_area, area + (size_t)(e * (n + 1) + i) * IPPM_FEAT * IPPM_FEAT);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -768,9 +728,6 @@ k_weighted_entropy(const ippm_config* __restrict__ c, const float* __restrict__ 
 // ======================================================================================================
 // host API
 // ======================================================================================================
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int grid1(size_t n, int b = 256) { return (int)((n + b - 1) / b); }
-
 static int fill_f32(ippm_ctx* ctx, float* p, float v, size_t n, hipStream_t st) {
   if (n == 0) return 0;
   if (n % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
@@ -917,7 +874,7 @@ extern "C" int ippm_sense_step(ippm_ctx* ctx, const int64_t* episode, const int3
     const int maps = agent_sel >= 0 ? n_envs : n_envs * c.n_agents;
     const int tail = sums ? grid1(n_envs) : 0;
     dim3 grid((unsigned)maps * split + tail);
-    IPPM_LAUNCH(ctx, IPPM_T_SENSE, (k_sense_update<1, 1, true>), grid, dim3(256), S_(stream), ctx->dcfg, episode, pos, truth, local, flips, code,
+    IPPM_LAUNCH(ctx, IPPM_T_SENSE, k_sense_update, grid, dim3(256), S_(stream), ctx->dcfg, episode, pos, truth, local, flips, code,
                 rect_in, rect_out, ws, area, sums, reward, ctx->dcounters, stage, agent_sel, split, maps, n_envs, ctx->n_active);
     IPPM_LAUNCH_CHECK("sense_update");
     return 0;

@@ -400,9 +400,6 @@ __global__ void k_entropy_maps(const ippm_config* __restrict__ c, const float* _
 // ======================================================================================================
 // host API
 // ======================================================================================================
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int grid1(size_t n, int b = 256) { return (int)((n + b - 1) / b); }
-
 // cells that column bin `bin` of an axis of n cells touches (its first and last cell may belong to it only in part)
 static inline int bin_cells(int bin, int n) {
   const long long lo = (long long)bin * n / IPPM_FEAT, hi = ((long long)(bin + 1) * n + IPPM_FEAT - 1) / IPPM_FEAT;

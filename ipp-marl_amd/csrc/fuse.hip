@@ -447,9 +447,6 @@ __global__ void k_reward_finalize(const ippm_config* __restrict__ c, double* __r
 // ======================================================================================================
 // host API
 // ======================================================================================================
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int grid1(size_t n, int b = 256) { return (int)((n + b - 1) / b); }
-
 // Rows per work item; the plan kernel (work list) and the fusion must agree, both derive it from (config, n_envs).
 // Sized so that a step yields roughly three items per wavefront slot of the chip (256 CUs x 4 SIMDs x 4 waves): about half
 // of the maps take part in a fusion and their op hulls span ~60 % of the grid's rows.  Fewer envs -> shorter runs -> the

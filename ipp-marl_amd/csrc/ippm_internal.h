@@ -13,6 +13,7 @@
 // words 8..15    : plan header written by the plan kernels
 // words 16..159  : op list, 8 words per op
 // IPPM_WS_WORDS (160) comes from ippmarl.h
+// (the planners read the state and store the op records as 16-byte words: the caller's ws should be 16-byte aligned)
 #define WS_FLAG_A 0   // region A may hold values outside [clip_lo, clip_hi]
 #define WS_RECT_A 1   // .. 1..4 = [yu,yd,xl,xr]
 #define WS_FLAG_S 5   // the agent's current footprint rect may hold out-of-range values (set by K3)
@@ -90,7 +91,8 @@ void ippm_timing_events(ippm_ctx* ctx, int cls, const char* name, hipEvent_t* a,
 #define IPPM_LAUNCH(ctx, cls, kern, grid, block, st, ...) IPPM_LAUNCH_SH(ctx, cls, kern, grid, block, 0, st, __VA_ARGS__)
 
 void ippm_set_error(const std::string& msg);
-// k_plan for local (global_maps == 0) or global fusion plans; step_small.hip
+static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }   // the C-ABI's stream argument
+static inline int grid1(size_t n, int b = 256) { return (int)((n + b - 1) / b); }           // workgroups of b threads for n items
 // Fusion work list (int32, caller-owned, ippm_work_words() long): [E] item counts, then [E][cap] items (map << 8 | run of
 // rows), cap = (N+1) * runs per map.  Every env owns its slice: the plan wavefront of env e WRITES count and items (no atomics,
 // nothing to clear between steps), the fusion's wavefronts each serve ONE env and stride through its list.

@@ -62,8 +62,6 @@ __global__ void k_td_lambda(const float* __restrict__ reward, const uint8_t* __r
   dr[idx] = (float)disc;
 }
 
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 extern "C" int ippm_coma_advantage(ippm_ctx* ctx, const float* probs, const float* q, const uint8_t* mask,
                                    const int32_t* action, float* advantage, float* pi_tilde, int32_t batch, void* stream) {
   if (!ctx || !probs || !q || !mask || !action || !advantage) { ippm_set_error("ippm_coma_advantage: null argument"); return -1; }

@@ -39,123 +39,65 @@ __device__ __forceinline__ bool comm_pair(const ippm_config* __restrict__ c, int
   return ok;
 }
 
-// row i of the comm matrix of env e: bit j set <=> agent i hears agent j; also stored as bytes
-__device__ __forceinline__ uint32_t comm_row(const ippm_config* __restrict__ c, const int64_t* __restrict__ episode,
-                                             const int32_t* pos_e, const float* __restrict__ comm_range,
-                                             const double* __restrict__ draws, uint8_t* __restrict__ comm, int t, int e, int i) {
-  const int n = c->n_agents;
-  const double range = comm_range ? (double)comm_range[e] : c->comm_range;
-  const int64_t ep = episode ? episode[e] : 0;
-  uint32_t row = 0;
-  for (int j = 0; j < n; ++j) {
-    const bool ok = comm_pair(c, ep, pos_e, range, draws, t, e, i, j);
-    comm[(size_t)(e * n + i) * n + j] = ok ? 1 : 0;
-    row |= ok ? (1u << j) : 0u;
-  }
-  return row;
-}
-
 __global__ void k_comm(const ippm_config* __restrict__ c, const int64_t* __restrict__ episode,
                        const int32_t* __restrict__ pos, const float* __restrict__ comm_range,
                        const double* __restrict__ draws, uint8_t* __restrict__ comm, int t, int n_envs) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = c->n_agents;
   if (tid >= n_envs * n) return;
-  const int e = tid / n;
-  comm_row(c, episode, pos + (size_t)e * n * 3, comm_range, draws, comm, t, e, tid % n);
+  const int e = tid / n, i = tid % n;   // row i of the comm matrix of env e: byte j set <=> agent i hears agent j
+  const double range = comm_range ? (double)comm_range[e] : c->comm_range;
+  const int64_t ep = episode ? episode[e] : 0;
+  uint8_t* out = comm + (size_t)(e * n + i) * n;
+  for (int j = 0; j < n; ++j) *out++ = comm_pair(c, ep, pos + (size_t)e * n * 3, range, draws, t, e, i, j) ? 1 : 0;
 }
 
 // ======================================================================================================
 // fusion planning (one lane per map): builds the ordered op list of K4 / K5 and maintains the
 // deferred-clamp state (the reference's full-grid input clip, applied only where it can matter)
 // ======================================================================================================
-__device__ __forceinline__ void plan_push(const ippm_config* __restrict__ c, int32_t* w, int& nops, int type, int src, int alt,
-                                          const int32_t* r, int& x0, int& x1, int& y0, int& y1, int4* s_ops) {
-  if (r[3] <= r[2] || r[1] <= r[0]) return;
-  if (s_ops) s_ops[nops] = make_int4(r[0], r[1], r[2], r[3]);  // LDS mirror of the rectangle for the tile builder
-  int32_t* op = w + WS_OPS + nops * OP_WORDS;
-  op[OP_TYPE] = type; op[OP_SRC] = src;
-  // the measurement's log-odds ride in the op record: the fusion kernel needs no dependent table lookup
-  op[OP_LM0] = type ? __float_as_int(c->logit_meas[alt][0]) : 0;
-  op[OP_LM1] = type ? __float_as_int(c->logit_meas[alt][1]) : 0;
-  op[OP_YU] = r[0]; op[OP_YD] = r[1]; op[OP_XL] = r[2]; op[OP_XR] = r[3];
-  x0 = min(x0, r[2]); x1 = max(x1, r[3]); y0 = min(y0, r[0]); y1 = max(y1, r[1]);
-  ++nops;
-}
+// Where agent j's footprint and the op record of its measurement come from.  The record {type, src, lm0, yu}, {yd, xl, xr, lm1} (the
+// OP_* layout; the measurement's log-odds ride in it: the fusion kernel needs no dependent table lookup) is the same for every map
+// that receives the measurement.
+// From the env's [N,4] published footprints and [N,3] positions (global memory or LDS): the record is derived op by op.
+struct plan_src_mem {
+  static constexpr bool mirrors = false;   // no tile builder behind it: s_ops / s_nops are null
+  const ippm_config* c;
+  const int32_t* rect_e;
+  const int32_t* pos_e;
+  __device__ __forceinline__ int4 rect(int j) const { return make_int4(rect_e[j * 4], rect_e[j * 4 + 1], rect_e[j * 4 + 2], rect_e[j * 4 + 3]); }
+  __device__ __forceinline__ void rec(int j, int4 r, int4& a, int4& b) const {
+    const int k = ippm_alt_index(c, pos_e[j * 3 + 2]);
+    a = make_int4(1, j, __float_as_int(c->logit_meas[k][0]), r.x);
+    b = make_int4(r.y, r.z, r.w, __float_as_int(c->logit_meas[k][1]));
+  }
+};
+// k_plan_step's tile form: lane j has prepared agent j's record once (s_rec: two int4 per agent, s_rect4: the footprints) and a map's
+// lane copies 32 bytes per received agent instead of re-deriving altitude index and table values op by op (the planning wavefront's
+// serial loop was 4 of the kernel's 12 us)
+struct plan_src_lds {
+  static constexpr bool mirrors = true;    // the plan's rectangles and their number go to s_ops / s_nops as well
+  const int4* s_rect4;
+  const int4* s_rec;
+  __device__ __forceinline__ int4 rect(int j) const { return s_rect4[j]; }
+  __device__ __forceinline__ void rec(int j, int4, int4& a, int4& b) const { a = s_rec[j * 2]; b = s_rec[j * 2 + 1]; }
+};
 
-// plans map i of env e (i == n: the global map); recv = agents whose measurements map i receives this step.
+// plans map i of env e (i == n_agents: the global map); recv = agents whose measurements map i receives this step.
 // Returns the number of rows of the plan's hull (0: nothing to fuse).
-// rect_e = the env's [N,4] published footprints, st = the map's first 6 workspace words (deferred-clamp state), both possibly
-// prefetched by the caller (global memory or LDS / registers).
-__device__ __forceinline__ int plan_map(const ippm_config* __restrict__ c, const int32_t* rect_e, const int32_t* pos_e, uint32_t recv,
-                                         int32_t* __restrict__ ws, int global_maps, int e, int i, const int32_t* st,
-                                         int4* s_ops = nullptr, int32_t* s_nops = nullptr, int n_act = -1) {
-  const int n_all = c->n_agents;
-  const int n = n_act >= 0 ? n_act : n_all;   // agents flying in this env (messages come from them only)
-  int32_t* w = ws + (size_t)(e * (n_all + 1) + i) * IPPM_WS_WORDS;
-  int nops = 0, x0 = 1 << 30, x1 = -1, y0 = 1 << 30, y1 = -1;
-  int last_src = -1;
-  for (int j = 0; j < n; ++j) {
-    bool take = global_maps ? true : (j != i && ((recv >> j) & 1u) != 0);
-    if (take) last_src = j;
-  }
-  int32_t* hdr = w + WS_PLAN;
-  const int whole = c->logit_prior != 0.f;
-  if (last_src < 0) {  // nothing received: the map is untouched; carry possible out-of-range regions forward
-    if (!global_maps && st[WS_FLAG_S]) {
-      const int32_t* ri = rect_e + i * 4;
-      if (st[WS_FLAG_A]) {
-        w[WS_RECT_A + 0] = min(st[WS_RECT_A + 0], ri[0]); w[WS_RECT_A + 1] = max(st[WS_RECT_A + 1], ri[1]);
-        w[WS_RECT_A + 2] = min(st[WS_RECT_A + 2], ri[2]); w[WS_RECT_A + 3] = max(st[WS_RECT_A + 3], ri[3]);
-      } else {
-        for (int q = 0; q < 4; ++q) w[WS_RECT_A + q] = ri[q];
-      }
-      w[WS_FLAG_A] = 1;
-      w[WS_FLAG_S] = 0;
-    }
-    hdr[PL_NOPS] = 0;
-    if (s_nops) *s_nops = 0;
-    return 0;
-  }
-  if (st[WS_FLAG_A]) plan_push(c, w, nops, 0, -1, 0, st + WS_RECT_A, x0, x1, y0, y1, s_ops);
-  if (!global_maps && st[WS_FLAG_S]) plan_push(c, w, nops, 0, -1, 0, rect_e + i * 4, x0, x1, y0, y1, s_ops);
-  int last_op = -1;
-  for (int j = 0; j < n; ++j) {
-    bool take = global_maps ? true : (j != i && ((recv >> j) & 1u) != 0);
-    if (!take) continue;
-    const int32_t* rj = rect_e + j * 4;
-    int before = nops;
-    plan_push(c, w, nops, 1, j, ippm_alt_index(c, pos_e[j * 3 + 2]), rj, x0, x1, y0, y1, s_ops);
-    if (j == last_src) {
-      last_op = nops > before ? nops - 1 : -1;  // an empty last footprint leaves no unclamped outputs
-      for (int q = 0; q < 4; ++q) w[WS_RECT_A + q] = rj[q];
-    }
-  }
-  w[WS_FLAG_A] = 0;  // set again by the fusion kernel if the last op leaves out-of-range values
-  w[WS_FLAG_S] = 0;
-  hdr[PL_NOPS] = nops;
-  if (s_nops) *s_nops = nops;
-  if (whole && nops > 0) { x0 = 0; x1 = c->grid_x; y0 = 0; y1 = c->grid_y; }
-  hdr[PL_X0] = x0; hdr[PL_X1] = x1; hdr[PL_Y0] = y0; hdr[PL_Y1] = y1;
-  hdr[PL_LAST] = last_op;
-  return nops > 0 ? x1 - x0 : 0;
-}
-
-// plan_map for k_plan_step: the op record of a measurement (type, source, log-odds of its altitude, footprint) is the same for
-// every map that receives it, so lane j has prepared it once (s_rec: two int4 per agent, s_rect4: the footprints) and a map's lane
-// copies 32 bytes per received agent instead of re-deriving altitude index and table values op by op (the planning wavefront's
-// serial loop was 4 of the kernel's 12 us).  Same results as plan_map, field by field.
-__device__ __forceinline__ int plan_map_fast(const ippm_config* __restrict__ c, const int4* s_rect4, const int4* s_rec, uint32_t recv,
-                                              int32_t* __restrict__ ws, int global_maps, int e, int i, const int32_t* st,
-                                              int4* s_ops, int32_t* s_nops, int n_act) {
-  const int n = n_act;    // agents flying in this env (messages come from them only); strides use the configured team size
+// n = the agents flying in this env (messages come from them only; strides use the configured team size), st = the map's first 6
+// workspace words (deferred-clamp state), prefetched by the caller; s_ops / s_nops = LDS mirror of the plan's rectangles and
+// their number for the tile builder (written when SRC::mirrors: a null test on a pointer into LDS is not free).
+template <class SRC>
+__device__ __forceinline__ int plan_map(const ippm_config* __restrict__ c, const SRC src, uint32_t recv, int32_t* __restrict__ ws,
+                                        int global_maps, int e, int i, const int32_t* st, int4* s_ops, int32_t* s_nops, int n) {
   int32_t* w = ws + (size_t)(e * (c->n_agents + 1) + i) * IPPM_WS_WORDS;
   const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
   const uint32_t takes = global_maps ? all : (recv & ~(1u << i) & all);
   int32_t* hdr = w + WS_PLAN;
   if (takes == 0) {  // nothing received: the map is untouched; carry possible out-of-range regions forward
     if (!global_maps && st[WS_FLAG_S]) {
-      const int4 ri = s_rect4[i];
+      const int4 ri = src.rect(i);
       if (st[WS_FLAG_A]) {
         w[WS_RECT_A + 0] = min(st[WS_RECT_A + 0], ri.x); w[WS_RECT_A + 1] = max(st[WS_RECT_A + 1], ri.y);
         w[WS_RECT_A + 2] = min(st[WS_RECT_A + 2], ri.z); w[WS_RECT_A + 3] = max(st[WS_RECT_A + 3], ri.w);
@@ -166,33 +108,34 @@ __device__ __forceinline__ int plan_map_fast(const ippm_config* __restrict__ c, 
       w[WS_FLAG_S] = 0;
     }
     hdr[PL_NOPS] = 0;
-    *s_nops = 0;
+    if (SRC::mirrors) *s_nops = 0;
     return 0;
   }
   const int last_src = 31 - __clz(takes);
   int nops = 0, x0 = 1 << 30, x1 = -1, y0 = 1 << 30, y1 = -1;
   int4* ops = reinterpret_cast<int4*>(w + WS_OPS);
-  auto clamp_op = [&](int4 r) {   // an op that only clips (type 0)
-    if (r.w <= r.z || r.y <= r.x) return;
-    s_ops[nops] = r;
-    ops[nops * 2] = make_int4(0, -1, 0, r.x);
-    ops[nops * 2 + 1] = make_int4(r.y, r.z, r.w, 0);
+  auto empty = [](int4 r) { return r.w <= r.z || r.y <= r.x; };   // r = {yu, yd, xl, xr}: an empty rectangle makes no op
+  auto push = [&](int4 r, int4 a, int4 b) {
+    if (SRC::mirrors) s_ops[nops] = r;
+    ops[nops * 2] = a;
+    ops[nops * 2 + 1] = b;
     x0 = min(x0, r.z); x1 = max(x1, r.w); y0 = min(y0, r.x); y1 = max(y1, r.y);
     ++nops;
   };
+  auto clamp_op = [&](int4 r) {   // an op that only clips (type 0)
+    if (!empty(r)) push(r, make_int4(0, -1, 0, r.x), make_int4(r.y, r.z, r.w, 0));
+  };
   if (st[WS_FLAG_A]) clamp_op(make_int4(st[WS_RECT_A], st[WS_RECT_A + 1], st[WS_RECT_A + 2], st[WS_RECT_A + 3]));
-  if (!global_maps && st[WS_FLAG_S]) clamp_op(s_rect4[i]);
+  if (!global_maps && st[WS_FLAG_S]) clamp_op(src.rect(i));
   int last_op = -1;
   for (uint32_t rem = takes; rem != 0; rem &= rem - 1u) {
     const int j = __ffs(rem) - 1;
-    const int4 r = s_rect4[j];
-    const bool some = r.w > r.z && r.y > r.x;
+    const int4 r = src.rect(j);
+    const bool some = !empty(r);
     if (some) {
-      s_ops[nops] = r;
-      ops[nops * 2] = s_rec[j * 2];
-      ops[nops * 2 + 1] = s_rec[j * 2 + 1];
-      x0 = min(x0, r.z); x1 = max(x1, r.w); y0 = min(y0, r.x); y1 = max(y1, r.y);
-      ++nops;
+      int4 a, b;
+      src.rec(j, r, a, b);
+      push(r, a, b);
     }
     if (j == last_src) {
       last_op = some ? nops - 1 : -1;  // an empty last footprint leaves no unclamped outputs
@@ -202,7 +145,7 @@ __device__ __forceinline__ int plan_map_fast(const ippm_config* __restrict__ c, 
   w[WS_FLAG_A] = 0;  // set again by the fusion kernel if the last op leaves out-of-range values
   w[WS_FLAG_S] = 0;
   hdr[PL_NOPS] = nops;
-  *s_nops = nops;
+  if (SRC::mirrors) *s_nops = nops;
   if (c->logit_prior != 0.f && nops > 0) { x0 = 0; x1 = c->grid_x; y0 = 0; y1 = c->grid_y; }
   hdr[PL_X0] = x0; hdr[PL_X1] = x1; hdr[PL_Y0] = y0; hdr[PL_Y1] = y1;
   hdr[PL_LAST] = last_op;
@@ -223,7 +166,7 @@ __global__ void k_plan(const ippm_config* __restrict__ c, const int32_t* __restr
     for (int j = 0; j < n; ++j) recv |= comm[(size_t)(e * n + i) * n + j] ? (1u << j) : 0u;
   int32_t st[6];
   for (int q = 0; q < 6; ++q) st[q] = ws[(size_t)(e * (n + 1) + i) * IPPM_WS_WORDS + q];
-  plan_map(c, rect + (size_t)e * n * 4, pos + (size_t)e * n * 3, recv, ws, global_maps, e, i, st);
+  plan_map(c, plan_src_mem{c, rect + (size_t)e * n * 4, pos + (size_t)e * n * 3}, recv, ws, global_maps, e, i, st, nullptr, nullptr, n);
 }
 
 // ======================================================================================================
@@ -406,7 +349,7 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
             const float* __restrict__ probs,
             const int32_t* __restrict__ action_in, uint8_t* __restrict__ mask, int32_t* __restrict__ action,
             int32_t* __restrict__ fault, int32_t* __restrict__ rect_next, int agent_sel, int32_t* __restrict__ work,
-            int wave_rows, int env_cap, unsigned long long* __restrict__ /* counters: not used here */, const int32_t* __restrict__ n_active,
+            int wave_rows, int env_cap, const int32_t* __restrict__ n_active,
             int32_t* __restrict__ slabs, int n_slabs, int tile_round) {
   // (argument order = latency order: what the first loads need -- positions, footprints, the maps' clamp state, the team size --
   // arrives in SGPRs with the wavefront, so the loads go out before anything else has been read)
@@ -426,7 +369,7 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
   __shared__ int32_t s_pos[IPPM_MAX_AGENTS * 3];    // pre-move positions: what comm and the plans see
   __shared__ int32_t s_pos1[IPPM_MAX_AGENTS * 3];   // K1's working copy (moved in place)
   __shared__ int4 s_rect4[IPPM_MAX_AGENTS];
-  __shared__ int4 s_rec[IPPM_MAX_AGENTS * 2];        // per agent: the op record of its measurement (plan_map_fast)
+  __shared__ int4 s_rec[IPPM_MAX_AGENTS * 2];        // per agent: the op record of its measurement (plan_src_lds)
   int32_t* s_rect = reinterpret_cast<int32_t*>(s_rect4);
   __shared__ int4 s_ops[(IPPM_MAX_AGENTS + 1) * IPPM_MAX_OPS];   // the op rectangles of every plan, for the tile builders
   __shared__ int32_t s_nops[IPPM_MAX_AGENTS + 1];
@@ -488,15 +431,17 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
     }
     if (tiled) {
       wave_sync_lds();
+      const plan_src_lds src{s_rect4, s_rec};
       if ((flags & IPPM_STEP_COMM) && lane < na && (agent_sel < 0 || agent_sel == lane))
-        hull_rows = plan_map_fast(c, s_rect4, s_rec, recv, ws, 0, e, lane, st, s_ops + lane * IPPM_MAX_OPS, s_nops + lane, na);
+        hull_rows = plan_map(c, src, recv, ws, 0, e, lane, st, s_ops + lane * IPPM_MAX_OPS, s_nops + lane, na);
       if ((flags & IPPM_STEP_GLOBAL) && lane == n)
-        hull_rows = plan_map_fast(c, s_rect4, s_rec, 0u, ws, 1, e, n, st, s_ops + n * IPPM_MAX_OPS, s_nops + n, na);
+        hull_rows = plan_map(c, src, 0u, ws, 1, e, n, st, s_ops + n * IPPM_MAX_OPS, s_nops + n, na);
     } else {
+      const plan_src_mem src{c, s_rect, s_pos};
       if ((flags & IPPM_STEP_COMM) && lane < na && (agent_sel < 0 || agent_sel == lane))
-        hull_rows = plan_map(c, s_rect, s_pos, recv, ws, 0, e, lane, st, nullptr, nullptr, na);
+        hull_rows = plan_map(c, src, recv, ws, 0, e, lane, st, nullptr, nullptr, na);
       if ((flags & IPPM_STEP_GLOBAL) && lane == n)
-        hull_rows = plan_map(c, s_rect, s_pos, 0u, ws, 1, e, n, st, nullptr, nullptr, na);
+        hull_rows = plan_map(c, src, 0u, ws, 1, e, n, st, nullptr, nullptr, na);
     }
     // an agent that does not fly (any more: team sizes may change between steps) gets an EMPTY plan, so that a fusion which
     // enumerates every map's plan from ws (no work list) never re-applies the plan it was left with when it last flew
@@ -598,9 +543,6 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
 // ======================================================================================================
 // host API
 // ======================================================================================================
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int grid1(size_t n, int b = 256) { return (int)((n + b - 1) / b); }
-
 int ippm_launch_plan(ippm_ctx* ctx, const int32_t* rect, const int32_t* pos, const uint8_t* comm, int32_t* ws, int global_maps,
                      int n_envs, int agent_sel, hipStream_t st) {
   const int maps = (global_maps || agent_sel >= 0) ? n_envs : n_envs * ctx->cfg.n_agents;
@@ -648,6 +590,17 @@ extern "C" int ippm_work_words(ippm_ctx* ctx, int32_t n_envs, int64_t* words) {
   return 0;
 }
 
+// what K1's policy needs, reported under the name of the entry point that was called
+static int policy_checks(const char* who, int policy, const int32_t* action_in, const float* probs, const int64_t* episode) {
+  const char* what = policy == 0 && !action_in ? ": policy 0 needs action_in"
+                     : (policy == 2 || policy == 3) && !probs ? ": policy 2/3 needs probs"
+                     : (policy == 1 || policy == 2) && !episode ? ": sampling needs episode ids"
+                     : (policy < 0 || policy > 3) ? ": unknown policy" : nullptr;
+  if (!what) return 0;
+  ippm_set_error(std::string(who) + what);
+  return -1;
+}
+
 extern "C" int ippm_plan_step(ippm_ctx* ctx, const int64_t* episode, int32_t* pos, const float* comm_range, const double* draws,
                               uint8_t* comm, const int32_t* rect, int32_t* ws, int32_t t, int32_t flags, const float* probs,
                               const int32_t* action_in, int32_t policy, uint8_t* mask, int32_t* action, int32_t* fault,
@@ -665,10 +618,7 @@ extern "C" int ippm_plan_step(ippm_ctx* ctx, const int64_t* episode, int32_t* po
   if ((flags & IPPM_STEP_GLOBAL) && (!rect || !ws)) { ippm_set_error("ippm_plan_step: global plan needs rect, ws"); return -1; }
   if (flags & IPPM_STEP_MOVE) {
     if (!mask || !action) { ippm_set_error("ippm_plan_step: move needs mask, action"); return -1; }
-    if (policy == 0 && !action_in) { ippm_set_error("ippm_plan_step: policy 0 needs action_in"); return -1; }
-    if ((policy == 2 || policy == 3) && !probs) { ippm_set_error("ippm_plan_step: policy 2/3 needs probs"); return -1; }
-    if ((policy == 1 || policy == 2) && !episode) { ippm_set_error("ippm_plan_step: sampling needs episode ids"); return -1; }
-    if (policy < 0 || policy > 3) { ippm_set_error("ippm_plan_step: unknown policy"); return -1; }
+    if (int rc = policy_checks("ippm_plan_step", policy, action_in, probs, episode)) return rc;
   }
   if (n_envs <= 0) return 0;
   const bool plans = (flags & (IPPM_STEP_COMM | IPPM_STEP_GLOBAL)) != 0;
@@ -692,7 +642,7 @@ extern "C" int ippm_plan_step(ippm_ctx* ctx, const int64_t* episode, int32_t* po
   IPPM_LAUNCH(ctx, IPPM_T_PLAN, k_plan_step, dim3(n_envs), dim3(64 * plan_waves), S_(stream), pos, rect, ws, ctx->cfg.n_agents, flags, t, policy,
                      ctx->dcfg, episode, comm_range, draws, comm, probs, action_in, mask, action, fault, rect_next, -1, plans ? work : nullptr,
                      ippm_fuse_wave_rows(ctx, n_envs), (flags & IPPM_STEP_TILES) ? ippm_tile_env_cap(ctx) : ippm_work_env_cap(ctx, n_envs),
-                     ctx->dcounters, ctx->n_active, ctx->slabs, ippm_slab_count(ctx),
+                     ctx->n_active, ctx->slabs, ippm_slab_count(ctx),
                      ctx->tl ? -1 : (tile_round ? 7 : 0));   // tile_build_map's round_mask
   IPPM_LAUNCH_CHECK("plan_step");
   return 0;
@@ -714,10 +664,7 @@ extern "C" int ippm_mask_act_move(ippm_ctx* ctx, const int64_t* episode, int32_t
                                   const int32_t* action_in, int32_t policy, int32_t t, uint8_t* mask, int32_t* action,
                                   int32_t* fault, int32_t n_envs, void* stream) {
   if (!ctx || !pos || !mask || !action) { ippm_set_error("ippm_mask_act_move: null argument"); return -1; }
-  if (policy == 0 && !action_in) { ippm_set_error("ippm_mask_act_move: policy 0 needs action_in"); return -1; }
-  if ((policy == 2 || policy == 3) && !probs) { ippm_set_error("ippm_mask_act_move: policy 2/3 needs probs"); return -1; }
-  if ((policy == 1 || policy == 2) && !episode) { ippm_set_error("ippm_mask_act_move: sampling needs episode ids"); return -1; }
-  if (policy < 0 || policy > 3) { ippm_set_error("ippm_mask_act_move: unknown policy"); return -1; }
+  if (int rc = policy_checks("ippm_mask_act_move", policy, action_in, probs, episode)) return rc;
   return ippm_plan_step(ctx, episode, pos, nullptr, nullptr, nullptr, nullptr, nullptr, t, IPPM_STEP_MOVE, probs, action_in, policy,
                         mask, action, fault, nullptr, nullptr, n_envs, stream);
 }

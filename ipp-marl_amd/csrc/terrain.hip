@@ -5,8 +5,6 @@
 
 #define IPPM_DOMAIN_TERRAIN 3u
 
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // Standard-normal white noise, four cells per Philox block (two Box-Muller pairs).  The stream depends on
 // (seed, episode, cell) only, so an episode's terrain does not depend on the batch it is generated in.
 __global__ __launch_bounds__(256) void k_terrain_noise(const ippm_config* __restrict__ c, const int64_t* __restrict__ episode,

@@ -910,14 +910,48 @@ def test_split_streams_run_side_by_side():
     del keep
 
 
-def test_fused_comm_and_plan_equals_separate_calls():
-    """ippm_comm_fuse_local == ippm_comm_matrix + ippm_fuse_local (bitwise), incl. link failures and per-episode ranges."""
+def _global_plan(ws):
+    """The global slot's plan as the planner left it: header words 8..13 and the op records, those beyond PL_NOPS zeroed."""
+    g = ws[:, -1]
+    ops = g[:, 16:].reshape(g.shape[0], -1, 8)
+    live = torch.arange(ops.shape[1], device=ws.device)[None, :] < g[:, 8, None]
+    return g[:, 8:14].clone(), ops * live[:, :, None]
+
+
+def _plan_branches(ws):
+    """(maps whose plan holds a clamp-only op, maps that received nothing and carry an out-of-range region forward), from ws.
+    The second is an upper bound on runs of the planner's carry branch: a map whose WS_FLAG_A an earlier fusion set and that merely
+    received nothing counts too (after a noise-free K3, which sets WS_FLAG_S at every step, the branch does run)."""
+    nops, types = ws[..., 8], ws[..., 16::8]                 # PL_NOPS; OP_TYPE of every op record
+    live = torch.arange(types.shape[-1], device=ws.device) < nops[..., None]
+    return int(((types == 0) & live).any(-1).sum()), int(((nops == 0) & (ws[..., 0] == 1)).sum())
+
+
+NOISE_FREE = dict(experiment__constraints__min_altitude=15, experiment__constraints__max_altitude=20, experiment__constraints__num_actions=27)
+
+
+@pytest.mark.parametrize("over,tile_form,expect_clamps", [
+    pytest.param({}, True, False, id="links_fail"),
+    # 20 m: the sensor is noise-free there, so WS_FLAG_S / WS_FLAG_A and the clamp-only ops occur from the first steps.  (From 15 m up the
+    # grid is 43 cells wide: one cell per lane, no tile form -- k_plan_step plans from memory like k_plan.)
+    pytest.param(NOISE_FREE, False, True, id="noise_free"),
+    # the same on the 128-cell grid (5 .. 20 m), where k_plan_step's tile form takes its op records from LDS
+    pytest.param(dict(NOISE_FREE, experiment__constraints__min_altitude=5), True, True, id="noise_free_tiles"),
+    # prior != 0.5: no tile form either, and every plan's hull is the whole grid
+    pytest.param(dict(mapping__prior=0.3), False, False, id="no_tile_form"),
+])
+def test_fused_comm_and_plan_equals_separate_calls(over, tile_form, expect_clamps):
+    """ippm_comm_fuse_local == ippm_comm_matrix + ippm_fuse_local (bitwise), incl. link failures and per-episode ranges; the plans of
+    k_plan_step (env a) against those of k_plan (env b) word for word, local slots and global slot."""
     from ippmarl.vec_env import POLICY_UNIFORM
-    params = make_params("small", experiment__uav__failure_rate=0.3, experiment__uav__fix_range=False, experiment__missions__n_agents=5)
+    params = make_params("small", experiment__uav__failure_rate=0.3, experiment__uav__fix_range=False, experiment__missions__n_agents=5,
+                         **over)
     a, b = _env(params, 24), _env(params, 24)
+    assert a._tile_form == tile_form, (a.d.grid_x, a.d.grid_y)    # which of k_plan_step's two sources of op records the case drives
     eps = np.arange(3, 27)
     a.reset(eps)
     b.reset(eps)
+    clamp_plans = carried = 0
     for t in range(a.d.budget + 1):
         a.build_observations(t, features=False)          # fused entry point
         b.comm_matrix(t)
@@ -926,16 +960,27 @@ def test_fused_comm_and_plan_equals_separate_calls():
         assert torch.equal(a.comm, b.comm) and torch.equal(a.local, b.local), t
         for lo, hi in ((0, 6), (8, 14), (16, None)):
             assert torch.equal(a.ws[:, :-1, lo:hi], b.ws[:, :-1, lo:hi]), (t, lo)
+        counts = _plan_branches(a.ws)
+        clamp_plans, carried = clamp_plans + counts[0], carried + counts[1]
+        # The two sequences plan the global map at different points: a with the local plans above, b inside ippm_fuse_global_reward
+        # below.  Each side's global slot is taken right after its own planner ran (a.steps plans nothing: K1 and K3 only).
+        a_hdr, a_ops = _global_plan(a.ws)
         a.steps(t, policy=POLICY_UNIFORM, features=False)
         # b: the stand-alone K5 entry point (plan + fusion + finalize), then K1 and K3 through the step's own kernels
         b.ctx.call("ippm_fuse_global_reward", b._p(b.glob), b._p(b.code), b._p(b.rect), b._p(b.pos), b._p(b.ws), b._p(b.sums),
                    b._p(b.reward), b.E, b.stream)
+        b_hdr, b_ops = _global_plan(b.ws)
+        assert torch.equal(a_hdr, b_hdr) and torch.equal(a_ops, b_ops), t
+        assert int(a_hdr[:, 0].min()) > 0, t             # every agent's measurement goes into the global map
         rb = b.reward.clone()
         b.ctx.call("ippm_mask_act_move", b._p(b.episode), b._p(b.pos), None, None, POLICY_UNIFORM, t, b._p(b.mask), b._p(b.action),
                    b._p(b.fault), b.E, b.stream)
         b.sense(stage=t + 1)
         assert torch.equal(a.pos, b.pos) and torch.equal(a.glob, b.glob) and torch.equal(a.local, b.local), t
         assert torch.equal(a.reward, rb) and torch.equal(a.rect, b.rect), t
+    print(f"plans with a clamp-only op: {clamp_plans}, maps that carried a region forward: {carried}")
+    if expect_clamps:   # the deferred clamp's branches were compared, not just passed by
+        assert clamp_plans > 0 and carried > 0, (clamp_plans, carried)
 
 
 @pytest.mark.parametrize("name,over,n_envs", [("small", {}, 6), ("c2", {}, 3), ("default", {"experiment__missions__n_agents": 3}, 2),
