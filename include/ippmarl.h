@@ -20,7 +20,15 @@
  * Array layouts (E envs, N agents, A actions, S = cfg.tile_stride)
  *   episode   int64  [E]          episode number of each env (seeds truth, start states, Philox streams)
  *   pos       int32  [E,N,3]      UAV position in metres (x,y,z)
- *   rect      int32  [E,N,4]      clipped footprint [yu,yd,xl,xr], half-open when sliced (cameras.py:62-77)
+ *   rect      int32  [E,N,4]      clipped footprint [yu,yd,xl,xr], half-open when sliced (cameras.py:62-77).  The kernels take any
+ *                                 rectangle with 0 <= yu < yd <= gy-1, 0 <= xl < xr <= gx-1 (the reference's clip never includes the last
+ *                                 row or column) that is no larger than the largest footprint, yd-yu <= 2 max radius_y, xr-xl <= 2 max
+ *                                 radius_x (code tiles and K3's launch are sized from the radii): there is no minimum size, and nothing
+ *                                 ties it to the lattice.  An EMPTY rectangle (yd <= yu or xr <= xl) is an agent without a footprint:
+ *                                 K3 senses nothing for it and its message adds nothing to any map (with prior 0.5 that is the
+ *                                 reference's update with an all-0.5 map2communicate; with any other prior the reference would still
+ *                                 shift every cell by logit(prior) for such a message, the library does not: the reference has no agent
+ *                                 without a footprint).  The carried region ws[.., 1..4] may be any box inside the grid.
  *   truth     uint8  [E,TRB]      ground truth, BIT-PACKED: cell (x,y) = bit (x*gy+y) of the env's little-endian bit string,
  *                                 TRB = ceil(gx*gy/32)*4 bytes (ceil((gx*gy+8)/32)*4 when gy is not a multiple of 4: one spare byte
  *                                 behind the last cell's, for the 2-byte loads of groups that straddle a byte)
@@ -202,7 +210,9 @@ int ippm_sense_update(ippm_ctx* ctx, const int64_t* episode, const int32_t* pos,
 /* K3 as the closing kernel of a batched env step (COMAWrapper.steps' `agent.step` calls, coma_wrapper.py:106-134):
  * rect_in (optional) = the sense records ippm_plan_step wrote for the new positions, int32 [E,N,IPPM_SENSE_REC_WORDS] (the
  * footprint and the measurement constants of its altitude: saves the dependent pos -> lattice index -> centre-table and
- * pos -> altitude -> sensor-table loads in front of the map accesses); area (optional) = tracked area sums, updated for local[e,i];
+ * pos -> altitude -> sensor-table loads in front of the map accesses; when given, the record's footprint is the one sensed and
+ * published on every grid -- the z of `pos` must still be the record's altitude: the one-cell-per-lane kernel with area sums and
+ * the next step's plans take the measurement's log-odds from it); area (optional) = tracked area sums, updated for local[e,i];
  * sums + reward (optional, together) = complete the reward of the step's global fusion in the same launch
  * (what ippm_reward_finalize does; the fusion of ippm_fuse_step leaves it open). */
 int ippm_sense_step(ippm_ctx* ctx, const int64_t* episode, const int32_t* pos, const uint8_t* truth, float* local,

@@ -934,7 +934,10 @@ extern "C" int ippm_sense_step(ippm_ctx* ctx, const int64_t* episode, const int3
   else if (tl) IPPM_K3_F(false, true);             // (from here on the default shape: 4 wavefronts, 3 loads, parts first)
   else if (ctx->vec == 4 && mis) IPPM_K3_F(true, false);
   else if (ctx->vec == 4) IPPM_K3_F(false, false);
-  else if (flips) IPPM_K3(1, false, true, false, false, false, false);
+  // (one cell per lane: the sense records count here as in every other form -- until the constructed-rectangle tests this branch
+  //  ran without them and re-derived the footprint from `pos`, the same rectangle only as long as the records came from K1)
+  else if (flips) { if (rect_in) IPPM_K3(1, false, true, true, false, false, false); else IPPM_K3(1, false, true, false, false, false, false); }
+  else if (rect_in) IPPM_K3(1, false, false, true, false, false, false);
   else IPPM_K3(1, false, false, false, false, false, false);
 #undef IPPM_K3_F
 #undef IPPM_K3_R
