@@ -442,6 +442,22 @@ int ippm_ig_select(ippm_ctx* ctx, const int32_t* pos, const uint8_t* mask, const
 int ippm_f1_counts(ippm_ctx* ctx, const float* maps, const uint8_t* truth, int32_t maps_per_truth, float logodds_threshold,
                    int64_t* out, int32_t n_maps, void* stream);
 
+/* ---- scoring of belief maps: what every comparison script of the reference reports per step (coma_test.py:84-97,150-196,
+ * IG_baseline.py:84-97, random_baseline.py, lawn_mower.py), in ONE streaming read of the maps (4 B + 1 bit per cell).
+ *   maps     n_maps whole maps of gx*gy float log-odds in the context's map layout; map m is scored against truth[m / maps_per_truth]
+ *            (the bit-packed planes; maps_per_truth = 1 for global maps, N for the agents' local maps);
+ *   entropy  double [n_maps]: sum over the cells with truth bit 1 of H(sigmoid(clamp(L, +-logit_clip))) in bits -- the "eval" weighting
+ *            of utils/state.py:53-121 as IG_baseline.py:84-97 uses it; the mean over the target cells is entropy / (tp + fn);
+ *   counts   int64 [n_maps,3,3]: (tp, fp, fn) of the target class for the map thresholded at L > thr_k, thr = (+logodds_delta, 0,
+ *            -logodds_delta) (utils/utils.py:64-76; DESIGN.md section 7 on why +-1e-5 bracket the exactly-cancelled cells);
+ *   scratch  double [ippm_score_scratch(n_maps)], caller-owned: the per-part partial sums.
+ * Every output element is written (nothing to zero beforehand).  Deterministic: no atomics, and the parts a map is summed in depend on
+ * the grid only -- a map scores the same, bit for bit, alone and in any batch.  The entropy of a nearly saturated cell is evaluated in
+ * the planner's series form (relative error below 1e-6 up to the clip; the log2(1 + e) form of ippm_weighted_entropy loses 6e-5 there). */
+int ippm_score_scratch(ippm_ctx* ctx, int32_t n_maps, int64_t* doubles);
+int ippm_score_maps(ippm_ctx* ctx, const float* maps, const uint8_t* truth, int32_t maps_per_truth, float logodds_delta,
+                    double* entropy, int64_t* counts, double* scratch, int32_t n_maps, void* stream);
+
 /* Synthetic random-field terrain: the device ends of the spectral synthesis the reference performs for every episode
  * (mapping/ground_truths.py:16-40; mapping/simulations.py:34-40) and then overwrites with the half-plane split.  The
  * caller runs the two FFTs and the sqrt(P(k)) product between the calls (ippmarl/terrain.py uses rocFFT via torch.fft).

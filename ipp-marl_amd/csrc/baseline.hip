@@ -24,21 +24,12 @@ __device__ __forceinline__ ig_shift ig_make_shift(float ln, float lp) {
   k.k0p = __expf(k.s0); k.k0m = __expf(-k.s0);
   return k;
 }
-__device__ __forceinline__ float ig_entropy_from_e(float a, float e, float& rd) {  // H of |L| = a, e = exp(-a); rd = 1/(1+e)
-  const float d = 1.0f + e;
-  rd = __builtin_amdgcn_rcpf(d);
-  // log2(1 + e): for a saturated cell e = 1e-4, and 1 + e rounded to float32 keeps only three digits of e -- the series
-  // log2(e_) (e - e^2/2 + e^3/3 - e^4/4) below 2^-6 (remainder < 2e-10) keeps them all.  It matters here and not in the reward
-  // terms: a candidate over cells that are all saturated has a gain made of nothing but such entropies' differences.
-  const float lg = e < 0.015625f ? e * (1.44269504f + e * (-0.72134752f + e * (0.48089835f - 0.36067376f * e))) : __log2f(d);
-  return lg + (a * 1.44269504f) * (e * rd);
-}
 __device__ __forceinline__ float ig_cell(float l, const ig_shift& k, float ec, float lc, float wt) {
   const float a = fabsf(l), e = __expf(-a), re = __builtin_amdgcn_rcpf(e);
   const bool pos = l >= 0.f;
   const float en = pos ? e : re, ep = pos ? re : e;   // exp(-l), exp(l)
   float rd;
-  const float hh = ig_entropy_from_e(a, e, rd);
+  const float hh = ippm_entropy_from_e(a, e, rd);
   const float pb = pos ? rd : e * rd;                  // sigmoid(l)
   const float qb = pos ? e * rd : rd;                  // 1 - sigmoid(l), formed directly: `1.f - pb` of a saturated cell (pb = 0.9999)
                                                        // keeps 3 digits, and its branch then carries the whole gain of the cell
@@ -46,7 +37,7 @@ __device__ __forceinline__ float ig_cell(float l, const ig_shift& k, float ec, f
   // exp(-|l1|), exp(-|l0|), floored at exp(-clip) like the entropy's clipped argument
   const float e1 = fmaxf(l1 >= 0.f ? en * k.k1m : ep * k.k1p, ec), e0 = fmaxf(l0 >= 0.f ? en * k.k0p : ep * k.k0m, ec);
   float rd1, rd0;
-  const float h1 = ig_entropy_from_e(fminf(fabsf(l1), lc), e1, rd1), h0 = ig_entropy_from_e(fminf(fabsf(l0), lc), e0, rd0);
+  const float h1 = ippm_entropy_from_e(fminf(fabsf(l1), lc), e1, rd1), h0 = ippm_entropy_from_e(fminf(fabsf(l0), lc), e0, rd0);
   // inside the weight band |l1|, |l0| < clip, so e1 / e0 are the unfloored exponentials there
   const float s1 = l1 >= 0.f ? rd1 : e1 * rd1, s0 = l0 >= 0.f ? rd0 : e0 * rd0;
   const float cw1 = l1 > wt ? 1.f : (l1 < -wt ? 0.f : s1);

@@ -211,6 +211,17 @@ __device__ __forceinline__ float ippm_entropy_l(float l, float lc) {
   const float d = 1.0f + e;
   return __log2f(d) + (a * 1.44269504f) * (e * __builtin_amdgcn_rcpf(d));
 }
+// The same entropy from a = min(|L|, lc) and e = exp(-a) already at hand, with log2(1 + e) as a series where e is small:
+__device__ __forceinline__ float ippm_entropy_from_e(float a, float e, float& rd) {  // H of |L| = a, e = exp(-a); rd = 1/(1+e)
+  const float d = 1.0f + e;
+  rd = __builtin_amdgcn_rcpf(d);
+  // log2(1 + e): for a saturated cell e = 1e-4, and 1 + e rounded to float32 keeps only three digits of e -- the series
+  // log2(e_) (e - e^2/2 + e^3/3 - e^4/4) below 2^-6 (remainder < 2e-10) keeps them all.  It matters where saturated cells carry the
+  // result and not in the reward terms: a planner's candidate over cells that are all saturated has a gain made of nothing but such
+  // entropies' differences (baseline.hip), and a well-explored map's target entropy is a sum of them (score.hip).
+  const float lg = e < 0.015625f ? e * (1.44269504f + e * (-0.72134752f + e * (0.48089835f - 0.36067376f * e))) : __log2f(d);
+  return lg + (a * 1.44269504f) * (e * rd);
+}
 // Shannon entropy of sigmoid(clamp(l)) in float64 (SHIFT path of the fusion, mapping.prior != 0.5: the float32 form's 1e-7 absolute
 // error per cell, summed over a whole grid of barely changed cells, would show at 1e-4 in the returns)
 __device__ __forceinline__ double entropy_l_f64(float l, float lc) {

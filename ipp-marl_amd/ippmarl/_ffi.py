@@ -105,6 +105,8 @@ PROTOTYPES = {
     "ippm_ig_candidates": [P, P, P, P, P, I32, P],
     "ippm_ig_select": [P, P, P, P, I32, P, P, I32, P],
     "ippm_f1_counts": [P, P, P, I32, C.c_float, P, I32, P],
+    "ippm_score_scratch": [P, I32, P],
+    "ippm_score_maps": [P, P, P, I32, C.c_float, P, P, P, I32, P],
     "ippm_terrain_noise": [P, P, P, I32, P],
     "ippm_terrain_spectrum": [P, P, P, P, I32, P],
     "ippm_terrain_field": [P, P, P, P, P, P, P, I32, P],

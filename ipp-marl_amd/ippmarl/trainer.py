@@ -448,6 +448,57 @@ class COMATrainer:
         return {"episode_return": float(ret.mean()), "absolute_return": float(abs_ret.mean()), "return_std": float(ret.std()),
                 "final_target_entropy": float(ent.mean()), "final_f1": float(f1.mean()), "faults": int(env.fault.ne(0).sum())}
 
+    def curves_on(self, episodes, policy: str = "actor", actions=None) -> Dict[str, torch.Tensor]:
+        """The per-step curves every comparison script of the reference reports (coma_test.py:84-97,150-196, IG_baseline.py:84-97,
+        random_baseline.py, lawn_mower.py), per env, for ``policy`` flown on the FIXED ``episodes`` (E ids): the policies of returns_on
+        plus "explicit", which flies ``actions`` (int [T,E,N]).  Like returns_on it does not touch the training buffer, the wave counter
+        or epsilon.
+          target_entropy [E,T+1], f1 [E,T+1], f1_counts [E,T+1,3,3] ((tp, fp, fn) at log-odds > +1e-5, 0, -1e-5): index 0 = the prior map,
+            index t+1 = the map holding every measurement up to the sensing after the move of step t (evaluate()'s convention);
+          episode_return [E], absolute_return [E]; actions [T,E,N], what was flown; faults [E] (the steps' fault words, or-ed).
+        No map is cloned per step: the env's own global fusion lags the sensing by one step, so the map of index t >= 1 IS ``env.glob``
+        right after build_observations(t) has launched step t's fusion -- it is scored there (VecEnv.score_maps), before steps(t) --
+        and only the last index needs the pending measurements fused into a copy (global_map_with_pending).  One host
+        synchronisation, at the end."""
+        from .vec_env import POLICY_EXPLICIT, POLICY_UNIFORM
+        if policy not in ("actor", "random", "ig", "explicit"):
+            raise ValueError(f"unknown policy {policy!r}")
+        env, T, E, N = self.env, self.T, self.E, self.N
+        if policy == "explicit":
+            if actions is None:
+                raise ValueError('curves_on(policy="explicit") needs actions [T,E,N]')
+            actions = torch.as_tensor(actions).to(self.device, torch.int32).reshape(T, E, N)
+        env.reset(torch.as_tensor(episodes, dtype=torch.int64).reshape(E))
+        ret = torch.zeros(E, device=self.device)
+        abs_ret = torch.zeros(E, device=self.device)
+        faults = torch.zeros(E, dtype=torch.int32, device=self.device)
+        flown = torch.empty(T, E, N, dtype=torch.int32, device=self.device)
+        scores = [env.score_maps()]            # the prior map
+        for t in range(T):
+            obs = env.build_observations(t, features=policy == "actor")
+            if t > 0:
+                scores.append(env.score_maps())
+            if policy == "actor":
+                with torch.no_grad():
+                    probs, _ = self.actor(obs.view(E * N, 11, 11, 7), self.eps_dev if self.graphs else self.eps)
+                reward, _, _ = env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(E, N, self.A), features=False)
+            elif policy == "ig":
+                reward, _, _ = env.steps(t, policy=POLICY_EXPLICIT, actions=env.ig_actions(communication=True), features=False)
+            elif policy == "explicit":
+                reward, _, _ = env.steps(t, policy=POLICY_EXPLICIT, actions=actions[t], features=False)
+            else:
+                reward, _, _ = env.steps(t, policy=POLICY_UNIFORM, features=False)
+            ret += reward[:, 0]
+            abs_ret += reward[:, 1]
+            faults |= env.fault
+            flown[t].copy_(env.action)
+        scores.append(env.score_maps(self.global_map_with_pending()))
+        out = {"target_entropy": torch.stack([s.target_entropy for s in scores], 1), "f1": torch.stack([s.f1 for s in scores], 1),
+               "f1_counts": torch.stack([s.counts for s in scores], 1), "episode_return": ret, "absolute_return": abs_ret,
+               "actions": flown, "faults": faults}
+        torch.cuda.current_stream(self.device).synchronize()
+        return out
+
     def save_actor(self, path: str):
         """Whole-module pickle of the actor, the reference's checkpoint format (coma_mission.py:425-451)."""
         from .checkpoint import save_actor

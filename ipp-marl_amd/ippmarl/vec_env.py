@@ -16,7 +16,7 @@ Philox4x32-10 keyed by (philox_seed; episode, agent, step) -- independent of how
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import os
 import time
@@ -93,6 +93,14 @@ def placement_stop_reason(scores, jumps: int = 0) -> Optional[str]:
     if k >= 12 and max(scores) < 1.02 * best and (jumps == 0 or jumps >= 2):
         return "no spread between the first draws"
     return None
+
+
+class MapScores(NamedTuple):
+    """What VecEnv.score_maps returns for M maps (device tensors)."""
+    entropy_sum: torch.Tensor      # float64 [M]: entropy in bits summed over the target cells
+    counts: torch.Tensor           # int64 [M,3,3]: (tp, fp, fn) of the target class at log-odds > (+delta, 0, -delta)
+    target_entropy: torch.Tensor   # float64 [M]: entropy_sum / max(tp + fn, 1), the mean over the target cells
+    f1: torch.Tensor               # float64 [M]: 2 tp / (2 tp + fp + fn) at threshold 0 (0 where nothing is predicted or true)
 
 
 class VecEnv:
@@ -537,6 +545,32 @@ class VecEnv:
         self._records[..., 4:6] = self._lm_table[k].view(torch.int32)
         self._agent_rewards(self._records)
         return self.agent_reward
+
+    # ---- evaluation metrics of belief maps (coma_test.py:84-97, IG_baseline.py:84-97, utils/utils.py:64-76) -----------
+    def score_maps(self, maps: Optional[torch.Tensor] = None, delta: float = 1e-5) -> MapScores:
+        """Target-region entropy and target-class F1 counts of whole maps against the envs' ground truth, in one streaming pass
+        (ippm_score_maps): ``maps`` = ``glob`` (default), ``local``, or any contiguous float32 tensor of whole maps in this env's storage
+        layout whose count is a multiple of E -- map m belongs to env m // (count / E).  The counts come at the log-odds thresholds
+        (+delta, 0, -delta): +-1e-5 leave out / take in the exactly-cancelled cells.  Deterministic (a map scores
+        the same alone and in any batch); does not synchronise."""
+        maps = self.glob if maps is None else maps
+        cells = self.d.grid_x * self.d.grid_y
+        if maps.dtype != torch.float32 or maps.device != self.device or not maps.is_contiguous():
+            raise ValueError("score_maps: a contiguous float32 tensor on the env's device")
+        M = maps.numel() // cells
+        if M == 0 or M * cells != maps.numel() or M % self.E:
+            raise ValueError(f"score_maps: whole maps of {self.d.grid_x} x {self.d.grid_y} cells, a multiple of {self.E} of them")
+        words = np.zeros(1, dtype=np.int64)
+        self.ctx.call("ippm_score_scratch", M, words.ctypes.data)
+        scratch = torch.empty(int(words[0]), dtype=torch.float64, device=self.device)
+        entropy = torch.empty(M, dtype=torch.float64, device=self.device)
+        counts = torch.empty(M, 3, 3, dtype=torch.int64, device=self.device)
+        self.ctx.call("ippm_score_maps", self._p(maps), self._p(self.truth), M // self.E, float(delta), self._p(entropy), self._p(counts),
+                      self._p(scratch), M, self.stream)
+        tp, fp, fn = counts[:, 1, 0].double(), counts[:, 1, 1].double(), counts[:, 1, 2].double()
+        den = 2 * tp + fp + fn
+        f1 = torch.where(den > 0, 2 * tp / den.clamp_min(1), torch.zeros_like(tp))   # (the rule of COMATrainer.map_metrics)
+        return MapScores(entropy, counts, entropy / (tp + fn).clamp_min(1), f1)
 
     # ---- greedy information-gain policy (IG_baseline.py:127-148, 222-325) for the whole batch ---------------------
     def ig_actions(self, communication: bool = True) -> torch.Tensor:
