@@ -419,6 +419,30 @@ int ippm_bias_relu_nhwc(float* x, const float* bias, int64_t rows, int32_t chann
 int ippm_bias_relu_backward_nhwc(const float* grad_y, const float* y, float* grad_x, float* grad_bias, int64_t rows,
                                  int32_t channels, void* stream);
 
+/* ---- native bf16 inference of the actor (actor/network.py:10-96): conv 5x5 -> 4x4 -> 4x4, fc1, fc3, softmax, epsilon mix, all on
+ * the matrix cores of gfx950.  No context needed.  Numerical contract: the input and the weights of every layer are rounded to bf16
+ * (nearest even), products accumulate in float32, the float32 bias is added to the accumulator, ReLU, and the activation is rounded to
+ * bf16 once, at the store; logits, softmax and (1 - eps) * softmax + eps / n_actions are float32.  Deterministic (fixed K order, no
+ * atomics, no split-K): a sample's outputs are the same bits alone, at any position of any batch, and from run to run.
+ *   ippm_actor_pack_bytes    size of the packed weight blob (n_actions in [1, 32]).
+ *   ippm_actor_pack          one kernel: the float32 parameters in PyTorch's layouts (conv*_w [O,C,kh,kw], fc*_w [O,I]; fc2 is unused by
+ *                            the network) -> packed (16-byte aligned): bf16 [O][K] per layer with K tap-major, channel-minor (conv1's
+ *                            K = 175 zero-padded to 192, fc3's rows zero-padded to 32; conv3 is the plain product over conv2's output
+ *                            flattened in (H, W, C) order), then the float32 biases.  Cheap and capturable: repack after every update.
+ *   ippm_actor_scratch_bytes size of the caller-owned scratch for batches up to `batch` (bf16 channels-last activations; the forward
+ *                            walks larger batches in slices of 4096 samples, so the scratch stays below 141 MB).
+ *   ippm_actor_forward       obs float [batch,11,11,7] (what ippm_actor_features writes) -> probs float [batch,n_actions] and, unless
+ *                            NULL, logits float [batch,n_actions].  eps_dev (device float, may be NULL: use eps) is read by the kernel, for
+ *                            callers that record the launch into a graph.  Any batch >= 1; every output element is written; the scratch
+ *                            needs no initialisation.  No host synchronisation, no allocation, launches on `stream` only. */
+int ippm_actor_pack_bytes(int32_t n_actions, int64_t* bytes);
+int ippm_actor_pack(const float* conv1_w, const float* conv1_b, const float* conv2_w, const float* conv2_b, const float* conv3_w,
+                    const float* conv3_b, const float* fc1_w, const float* fc1_b, const float* fc3_w, const float* fc3_b,
+                    int32_t n_actions, void* packed, void* stream);
+int ippm_actor_scratch_bytes(int64_t batch, int64_t* bytes);
+int ippm_actor_forward(const void* packed, const float* obs, int64_t batch, int32_t n_actions, float eps, const float* eps_dev,
+                       void* scratch, float* probs, float* logits, void* stream);
+
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
  * Q(s_t)[a_t] -> td_target, discounted_return float. */

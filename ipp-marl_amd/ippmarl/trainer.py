@@ -13,6 +13,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _ffi
+from .actor_native import NativeActor, resolve_mode
 from .learners import ActorLearner, CriticLearner
 from .networks import ActorNetwork, CriticNetwork, epsilon_schedule
 from .parallel import GradAllReducer, broadcast_module, episode_ids
@@ -22,8 +23,13 @@ from .vec_env import VecEnv, POLICY_ARGMAX, POLICY_SAMPLE
 class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
-                 terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None):
+                 terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None,
+                 actor_inference: Optional[str] = None):
         self.params = params
+        # actor_inference: "torch" (the float32 module, the default) or "native" (libippmarl's bf16 matrix-core forward for every
+        # no-grad use of the actor: actor_native.NativeActor); None reads IPPMARL_ACTOR_INFERENCE.  The update is float32 either way.
+        self.actor_inference = resolve_mode(actor_inference)
+        self._native = None
         # team_sizes: mixed team sizes in one batch (VecEnv): the transitions of agents that do not fly never enter a minibatch
         self.env = VecEnv(params, n_envs, device=device, philox_seed=philox_seed, terrain=terrain, team_sizes=team_sizes)
         # mission type DeepQ (coma_wrapper.py:113-171): every agent's transition carries ITS information gain (VecEnv.agent_reward, on
@@ -103,6 +109,8 @@ class COMATrainer:
         policy = POLICY_ARGMAX if mode == "eval" else POLICY_SAMPLE
         step_rewards, step_actions, step_altitudes = [], [], []
         replay = self._step_graphs is not None and mode == "train" and w == 0 and not self.keep_rollout_log
+        if replay and self.actor_inference == "native":
+            self.native_actor().sync()    # (weights written from the host since the last pack: the recorded steps read the pack)
         for t in range(self.T):
             if replay:
                 self._step_graphs[t].replay()
@@ -129,8 +137,7 @@ class COMATrainer:
         """One lock-step env step of all E envs: observations -> actor -> move + sense (+ the transition into the buffer)."""
         env = self.env
         obs = env.build_observations(t)
-        with torch.no_grad():
-            probs, _ = self.actor(obs.view(self.E * self.N, 11, 11, 7), eps)
+        probs = self._act(obs, eps)
         reward, done, state = env.steps(t, policy=policy, probs=probs.view(self.E, self.N, self.A))
         team = reward
         if self.deepq:
@@ -145,6 +152,27 @@ class COMATrainer:
         self.abs_ret += reward[:, 1]
         self.team_ret += team[:, 0]
         return reward
+
+    def _act(self, obs: torch.Tensor, eps) -> torch.Tensor:
+        """probs [E*N, A] of the current actor for the observations [E,N,11,11,7], without gradients, on the selected inference path."""
+        obs = obs.view(self.E * self.N, 11, 11, 7)
+        if self.actor_inference == "native":
+            return self.native_actor()(obs, eps)[0]
+        with torch.no_grad():
+            return self.actor(obs, eps)[0]
+
+    def native_actor(self):
+        """The NativeActor of ``self.actor`` (built on first use, rebuilt when ``self.actor`` has been replaced by another module)."""
+        if self._native is None or self._native.module is not self.actor:
+            self._native = NativeActor(self.actor, self.device)
+            self._native.reserve(self.E * self.N)
+        return self._native
+
+    def refresh_actor_inference(self):
+        """Repack the native actor from the module's current parameters (no-op on the torch path): update() does it after its
+        optimizer steps; call it after loading a state dict into ``self.actor`` by other means."""
+        if self.actor_inference == "native":
+            self.native_actor().refresh()
 
     def last_agent_reward(self) -> torch.Tensor:
         """[E, 2] DeepQ (relative, absolute) reward of the last agent that flies in each env: what the reference's wrapper returns
@@ -163,6 +191,10 @@ class COMATrainer:
             raise _ffi.IppmError("capture_graphs: one wave per update, one rank, hard target updates and one team size only")
         env = self.env
         env.profile = False
+        if self.actor_inference == "native":
+            # parameters written from the host since the last pack: repack NOW, while launches still execute (a repack that a captured
+            # step merely records would leave every eager forward after the capture on the old weights)
+            self.native_actor().sync()
         torch.cuda.synchronize(self.device)
         saved = {k: getattr(env, k).clone() for k in ("local", "glob", "ws", "sums", "pos", "pos_pre", "comm", "mask", "action", "fault",
                                                        "reward", "area", "rect", "rect_next", "code", "work")
@@ -321,6 +353,7 @@ class COMATrainer:
                 self.critic_learner.collect = self.actor_learner.collect = False
             if data_pass == 0 and eager:
                 self.train_step += 1
+        self.refresh_actor_inference()   # (recorded with the round when capture_graphs records it)
         return closs, aloss
 
     def train(self, n_updates: int, log=None):
@@ -394,8 +427,7 @@ class COMATrainer:
             team_ret = torch.zeros(self.E, device=self.device)
             for t in range(self.T):
                 obs = env.build_observations(t)
-                with torch.no_grad():
-                    probs, _ = self.actor(obs.view(self.E * self.N, 11, 11, 7), self.eps)
+                probs = self._act(obs, self.eps)
                 reward, _, _ = env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(self.E, self.N, self.A))
                 team_ret += reward[:, 0]
                 ret += (self.last_agent_reward() if self.deepq else reward)[:, 0]
@@ -433,8 +465,7 @@ class COMATrainer:
         for t in range(self.T):
             if policy == "actor":
                 obs = env.build_observations(t)
-                with torch.no_grad():
-                    probs, _ = self.actor(obs.view(self.E * self.N, 11, 11, 7), self.eps_dev if self.graphs else self.eps)
+                probs = self._act(obs, self.eps_dev if self.graphs else self.eps)
                 reward, _, _ = env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(self.E, self.N, self.A), features=False)
             elif policy == "ig":
                 env.build_observations(t, features=False)
@@ -479,8 +510,7 @@ class COMATrainer:
             if t > 0:
                 scores.append(env.score_maps())
             if policy == "actor":
-                with torch.no_grad():
-                    probs, _ = self.actor(obs.view(E * N, 11, 11, 7), self.eps_dev if self.graphs else self.eps)
+                probs = self._act(obs, self.eps_dev if self.graphs else self.eps)
                 reward, _, _ = env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(E, N, self.A), features=False)
             elif policy == "ig":
                 reward, _, _ = env.steps(t, policy=POLICY_EXPLICIT, actions=env.ig_actions(communication=True), features=False)
