@@ -443,6 +443,26 @@ int ippm_actor_scratch_bytes(int64_t batch, int64_t* bytes);
 int ippm_actor_forward(const void* packed, const float* obs, int64_t batch, int32_t n_actions, float eps, const float* eps_dev,
                        void* scratch, float* probs, float* logits, void* stream);
 
+/* ---- native bf16 inference of the critic (critic/network.py:12-47): the actor's trunk over the 12 planes of a critic state and fc3,
+ * in the actor's kernels and under the actor's numerical contract word for word (bf16 inputs and weights, float32 accumulation and bias,
+ * ReLU, one bf16 rounding at the store, fixed K order); Q is float32.  No softmax: the log_softmax over the batch that the reference's
+ * critic also returns is a logged metric and is not computed here.  No context needed.
+ *   ippm_critic_pack_bytes    size of the packed weight blob (n_actions in [1, 32]).
+ *   ippm_critic_pack          as ippm_actor_pack, for conv1_w [256,12,5,5]: conv1's K = 300 zero-padded to 320.
+ *   ippm_critic_scratch_bytes size of the caller-owned scratch for batches up to `batch` (slices of 4096 samples, as the actor's).
+ *   ippm_critic_forward       state float [batch,11,11,12] (what ippm_critic_features writes) -> q float [batch,n_actions] unless NULL,
+ *                             and, when action (int32 [batch]) and q_sel are given, q_sel[b] = q[b][action[b]] (float [batch]); an action
+ *                             outside [0, n_actions) gives NaN in q_sel[b] and reads nothing out of range.  An error when q and q_sel
+ *                             are both NULL, or q_sel is given without action.  Any batch >= 1; every output element is written; the
+ *                             scratch needs no initialisation.  No host synchronisation, no allocation, launches on `stream` only. */
+int ippm_critic_pack_bytes(int32_t n_actions, int64_t* bytes);
+int ippm_critic_pack(const float* conv1_w, const float* conv1_b, const float* conv2_w, const float* conv2_b, const float* conv3_w,
+                     const float* conv3_b, const float* fc1_w, const float* fc1_b, const float* fc3_w, const float* fc3_b,
+                     int32_t n_actions, void* packed, void* stream);
+int ippm_critic_scratch_bytes(int64_t batch, int64_t* bytes);
+int ippm_critic_forward(const void* packed, const float* state, int64_t batch, int32_t n_actions, const int32_t* action, void* scratch,
+                        float* q, float* q_sel, void* stream);
+
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
  * Q(s_t)[a_t] -> td_target, discounted_return float. */

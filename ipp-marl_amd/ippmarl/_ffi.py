@@ -106,6 +106,10 @@ PROTOTYPES = {
     "ippm_actor_pack": [P, P, P, P, P, P, P, P, P, P, I32, P, P],
     "ippm_actor_scratch_bytes": [I64, P],
     "ippm_actor_forward": [P, P, I64, I32, C.c_float, P, P, P, P, P],
+    "ippm_critic_pack_bytes": [I32, P],
+    "ippm_critic_pack": [P, P, P, P, P, P, P, P, P, P, I32, P, P],
+    "ippm_critic_scratch_bytes": [I64, P],
+    "ippm_critic_forward": [P, P, I64, I32, P, P, P, P, P],
     "ippm_ig_candidates": [P, P, P, P, P, I32, P],
     "ippm_ig_select": [P, P, P, P, I32, P, P, I32, P],
     "ippm_f1_counts": [P, P, P, I32, C.c_float, P, I32, P],

@@ -8,102 +8,35 @@ are float32.  Deterministic: a sample's probabilities are the same bits alone an
 ``actor_inference`` / ``IPPMARL_ACTOR_INFERENCE`` select the path: "torch" (default) or "native"."""
 from __future__ import annotations
 
-import ctypes as C
-import os
 from typing import Optional
 
 import torch
 
 from . import _ffi
+from .native_net import MODES, NativeNet, resolve  # noqa: F401
 
-MODES = ("torch", "native")
 ENV_VAR = "IPPMARL_ACTOR_INFERENCE"
-_LAYERS = ("conv1", "conv2", "conv3", "fc1", "fc3")   # fc2 is never used by the network (networks._ConvTrunk)
 
 
 def resolve_mode(actor_inference: Optional[str] = None) -> str:
-    """The inference path: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises."""
-    mode = actor_inference if actor_inference is not None else os.environ.get(ENV_VAR, "") or "torch"
-    if mode not in MODES:
-        raise ValueError(f"actor inference must be one of {MODES}, got {mode!r}")
-    return mode
+    """The actor's inference path: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises.
+    (The critic's switch: critic_native.resolve_mode.)"""
+    return resolve(actor_inference, ENV_VAR, "actor")
 
 
-class NativeActor:
-    """Holds the packed bf16 weights of ``actor_module`` and the forward's scratch on ``device``.  ``refresh()`` repacks from the
-    module's current parameters (one kernel, capturable); ``__call__(obs, eps)`` is the module's no-grad forward, ``-> (probs, None)``.
-    A call also repacks by itself when the parameters' version counters say that they were written since the last pack, so a
-    ``load_state_dict`` or an eager optimizer step cannot leave a stale pack behind; a replayed graph changes no counter, which is why the
-    trainer records ``refresh()`` into its update graph.  A repack that is only recorded during a capture does not count as a pack:
-    ``COMATrainer.capture_graphs`` repacks before it starts recording."""
+class NativeActor(NativeNet):
+    """Holds the packed bf16 weights of ``actor_module`` and the forward's scratch on ``device`` (native_net.NativeNet: ``refresh()``,
+    ``sync()``, ``reserve()`` and the rules that keep the pack current); ``__call__(obs, eps)`` is the module's no-grad forward,
+    ``-> (probs, None)``."""
 
-    def __init__(self, actor_module, device):
-        self.module = actor_module
-        self.device = self._device(device)
-        self.lib = _ffi.load_library()
-        self.n_actions = int(actor_module.fc3.out_features)
-        nbytes = C.c_int64(0)
-        _ffi.check(self.lib.ippm_actor_pack_bytes(self.n_actions, C.addressof(nbytes)), "ippm_actor_pack_bytes")
-        self.packed = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-        self.scratch = None
-        self._capacity = 0
-        self._stamp = None
-        self.refresh()
-
-    @staticmethod
-    def _device(device) -> torch.device:
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _ffi.IppmError("NativeActor: the native actor forward runs on the GPU only (there is no CPU fallback)")
-        return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
-
-    def _params(self):
-        out = []
-        for name in _LAYERS:
-            layer = getattr(self.module, name)
-            out += [layer.weight, layer.bias]
-        return out
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def refresh(self):
-        params = self._params()
-        for p in params:
-            if p.device != self.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _ffi.IppmError("NativeActor: the actor's parameters must be contiguous float32 tensors on the actor's device")
-        _ffi.check(self.lib.ippm_actor_pack(*[p.data_ptr() for p in params], self.n_actions, self.packed.data_ptr(), self._stream()),
-                   "ippm_actor_pack")
-        # (a launch that is only being RECORDED into a graph has packed nothing yet: the pack stays marked as it was, and the
-        #  next call outside the capture repacks if the parameters were written)
-        if not torch.cuda.is_current_stream_capturing():
-            self._stamp = [(p.data_ptr(), p._version) for p in params]
-
-    def sync(self):
-        """Repack if the parameters were written since the last pack (host-side check of their version counters)."""
-        if self._stamp != [(p.data_ptr(), p._version) for p in self._params()]:
-            self.refresh()
-
-    def reserve(self, batch: int):
-        """Scratch for batches up to ``batch`` (allocates; call it before a graph capture)."""
-        if batch > self._capacity:
-            nbytes = C.c_int64(0)
-            _ffi.check(self.lib.ippm_actor_scratch_bytes(int(batch), C.addressof(nbytes)), "ippm_actor_scratch_bytes")
-            if self.scratch is None or nbytes.value > self.scratch.numel():
-                self.scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            self._capacity = int(batch)
+    PREFIX, WHO, WHAT, PLANES = "ippm_actor", "NativeActor", "actor", _ffi.ACTOR_PLANES
 
     def forward(self, obs: torch.Tensor, eps=0.0, logits: bool = False):
         """obs float32 [B,11,11,7] -> (probs [B,A], logits [B,A] or None).  ``eps``: a float, or a 0-dim float32 device tensor that
         the kernel reads (what a recorded graph needs)."""
-        if obs.dim() == 3:
-            obs = obs.unsqueeze(0)
-        if obs.dtype != torch.float32 or tuple(obs.shape[1:]) != (_ffi.FEAT, _ffi.FEAT, _ffi.ACTOR_PLANES) or obs.device != self.device:
-            raise _ffi.IppmError(f"NativeActor: needs float32 observations [B,11,11,7] on {self.device}, got {tuple(obs.shape)} {obs.dtype}")
+        obs = self._input(obs)
         self.sync()
-        obs = obs.contiguous()
         B = obs.shape[0]
-        self.reserve(B)
         probs = torch.empty(B, self.n_actions, dtype=torch.float32, device=self.device)
         lg = torch.empty_like(probs) if logits else None
         eps_dev = None

@@ -39,6 +39,9 @@ class CriticLearner:
         self.optimizer.zero_grad()
         self.collect = False   # keep the tensors ippmarl.metrics.critic_metrics needs in self.last
         self.last = None
+        # optional inference hook (the trainer sets a critic_native.NativeCritic of ``critic``): the post-step Q of apply() then comes
+        # from its bf16 forward; None: the float32 module
+        self.inference = None
 
     def update_target_network(self, num_train_step: int, data_pass: int):
         """Hard copy every copy_rate train steps on data pass 0, or Polyak (critic/learner.py:192-198)."""
@@ -66,6 +69,9 @@ class CriticLearner:
         states, actions, td_targets, loss, q_chosen = self._pending
         self._pending = None
         self.optimizer.step()
+        if self.inference is not None and not self.collect:
+            return self.inference.after_step(states)
+        # (diagnostics keep the module's forward: the metrics need logp)
         with torch.no_grad():
             q_new, logp = self.critic(states)
         if self.collect:

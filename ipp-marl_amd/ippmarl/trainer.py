@@ -13,6 +13,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _ffi
+from . import critic_native
 from .actor_native import NativeActor, resolve_mode
 from .learners import ActorLearner, CriticLearner
 from .networks import ActorNetwork, CriticNetwork, epsilon_schedule
@@ -24,12 +25,16 @@ class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
                  terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None,
-                 actor_inference: Optional[str] = None):
+                 actor_inference: Optional[str] = None, critic_inference: Optional[str] = None):
         self.params = params
         # actor_inference: "torch" (the float32 module, the default) or "native" (libippmarl's bf16 matrix-core forward for every
         # no-grad use of the actor: actor_native.NativeActor); None reads IPPMARL_ACTOR_INFERENCE.  The update is float32 either way.
         self.actor_inference = resolve_mode(actor_inference)
         self._native = None
+        # critic_inference: the same switch for the no-grad uses of a critic (critic_native.NativeCritic): the TD targets and the
+        # post-step Q of every critic minibatch; None reads IPPMARL_CRITIC_INFERENCE.  The critic's loss and gradients are float32 either way.
+        self.critic_inference = critic_native.resolve_mode(critic_inference)
+        self._native_critic = self._native_target = None
         # team_sizes: mixed team sizes in one batch (VecEnv): the transitions of agents that do not fly never enter a minibatch
         self.env = VecEnv(params, n_envs, device=device, philox_seed=philox_seed, terrain=terrain, team_sizes=team_sizes)
         # mission type DeepQ (coma_wrapper.py:113-171): every agent's transition carries ITS information gain (VecEnv.agent_reward, on
@@ -93,6 +98,10 @@ class COMATrainer:
         self.keep_rollout_log = False
         self.last_rollout = None
         self.last_diagnostics = None
+        if self.critic_inference == "native":
+            self.critic_learner.inference = self._native_critic = critic_native.NativeCritic(self.critic, self.device)
+            self._native_critic.reserve(W * T * E * N)
+            self.native_target()
 
     # ------------------------------------------------------------------------------------------------
     def rollout(self, mode: str = "train") -> Dict[str, float]:
@@ -168,6 +177,20 @@ class COMATrainer:
             self._native.reserve(self.E * self.N)
         return self._native
 
+    def target_module(self):
+        """The critic whose Q the TD targets are built from: the never-synchronised copy taken at construction
+        (quirks="reference"), or the learner's target network."""
+        return self.frozen_target if self.quirks == "reference" else self.critic_learner.target_critic
+
+    def native_target(self):
+        """The NativeCritic of ``target_module()`` (rebuilt when that has become another module).  The frozen copy is packed once; the
+        learner's target network is repacked by ``sync()`` after a hard or soft update wrote it."""
+        target = self.target_module()
+        if self._native_target is None or self._native_target.module is not target:
+            self._native_target = critic_native.NativeCritic(target, self.device)
+            self._native_target.reserve(self.waves_per_update * self.T * self.E * self.N)
+        return self._native_target
+
     def refresh_actor_inference(self):
         """Repack the native actor from the module's current parameters (no-op on the torch path): update() does it after its
         optimizer steps; call it after loading a state dict into ``self.actor`` by other means."""
@@ -195,6 +218,9 @@ class COMATrainer:
             # parameters written from the host since the last pack: repack NOW, while launches still execute (a repack that a captured
             # step merely records would leave every eager forward after the capture on the old weights)
             self.native_actor().sync()
+        if self.critic_inference == "native":    # (the same for both critic packs; their scratch is as large as the buffer already)
+            self._native_critic.sync()
+            self.native_target().sync()
         torch.cuda.synchronize(self.device)
         saved = {k: getattr(env, k).clone() for k in ("local", "glob", "ws", "sums", "pos", "pos_pre", "comm", "mask", "action", "fault",
                                                        "reward", "area", "rect", "rect_next", "code", "work")
@@ -227,15 +253,18 @@ class COMATrainer:
         """K8 over one chain per (env, agent): the transitions of all buffered waves in time order
         (BatchMemory.build_td_targets, batch_memory.py:120-162)."""
         W, T, E, N = self.filled, self.T, self.E, self.N
-        target = self.frozen_target if self.quirks == "reference" else self.critic_learner.target_critic
+        target = self.target_module()
         states = self.buf_state[:W].reshape(W * T * E * N, 11, 11, 12)
         actions = self.buf_action[:W].reshape(-1)
-        q_sel = torch.empty(W * T * E * N, device=self.device)
-        with torch.no_grad():
-            chunk = 16384
-            for lo in range(0, states.shape[0], chunk):
-                q, _ = target(states[lo:lo + chunk])
-                q_sel[lo:lo + chunk] = q.view(-1, self.A).gather(1, actions[lo:lo + chunk].long().view(-1, 1)).squeeze(1)
+        if self.critic_inference == "native":
+            _, q_sel = self.native_target().forward(states, actions, want_q=False)    # one call: the kernel gathers the chosen Q
+        else:
+            q_sel = torch.empty(W * T * E * N, device=self.device)
+            with torch.no_grad():
+                chunk = 16384
+                for lo in range(0, states.shape[0], chunk):
+                    q, _ = target(states[lo:lo + chunk])
+                    q_sel[lo:lo + chunk] = q.view(-1, self.A).gather(1, actions[lo:lo + chunk].long().view(-1, 1)).squeeze(1)
         # chains: [E*N, W*T]
         q_sel = q_sel.view(W, T, E, N).permute(2, 3, 0, 1).reshape(E * N, W * T).contiguous()
         # (COMA: the env's team reward on each of its agents' chains; DeepQ: each agent's own)
@@ -262,6 +291,8 @@ class COMATrainer:
         if self._update_graph is not None and W == 1 and not diagnostics:
             # the recorded round: hard target copy (a host-side decision) first, fresh permutations into the graph's buffer, replay
             self.critic_learner.update_target_network(self.train_step, 0)
+            if self.critic_inference == "native":
+                self.native_target().sync()    # (the copy was written from the host: the recorded TD targets read the pack)
             for dp in range(self.data_passes):
                 self._perms[dp].copy_(torch.randperm(n, device=self.device))
             self._update_graph.replay()
