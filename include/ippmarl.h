@@ -463,6 +463,31 @@ int ippm_critic_scratch_bytes(int64_t batch, int64_t* bytes);
 int ippm_critic_forward(const void* packed, const float* state, int64_t batch, int32_t n_actions, const int32_t* action, void* scratch,
                         float* q, float* q_sel, void* stream);
 
+/* ---- conv2 of the learners' convnets on the bf16 matrix cores, for the COMA update (actor/network.py:19-28, critic/network.py): the
+ * stride-1, unpadded 4x4 convolution with 256 input and 256 output channels, forward and both gradients, over channels-last float32
+ * tensors: x [batch,ih,iw,256] with 4 <= ih, iw <= 11, y and gy [batch,ih-3,iw-3,256], w and gw in PyTorch's contiguous [256,256,4,4].
+ * Numerical contract: every operand tensor (x, w, gy) is rounded to bf16 (nearest even) on its way in, products accumulate in float32
+ * on mfma_f32_16x16x32_bf16, outputs are float32 and not rounded again; bias-free.  Deterministic: no float atomics, every output
+ * element has one owner and a fixed summation order; forward and input gradient of a sample do not depend on the batch around it, the
+ * weight gradient depends on the inputs and the batch size only (not on the device, the grid or the scratch's previous content).
+ *   ippm_conv4x4_bf16_scratch_bytes  size of the caller-owned scratch for `batch`: the two bf16 weight packs (4 MiB), then the weight
+ *                                    gradient's float32 partial sums, 4 MiB per chunk of IPPM_CONV4X4_WGRAD_CHUNK samples.  Forward and
+ *                                    input gradient use the packs only.  Needs no initialisation; every call repacks what it reads.
+ *   ippm_conv4x4_bf16_forward        y[b,oy,ox,o] = sum over ty,tx,c of x[b,oy+ty,ox+tx,c] * w[o,c,ty,tx].
+ *   ippm_conv4x4_bf16_grad_input     gx[b,iy,ix,c] = sum over the taps (ty,tx) with (iy-ty, ix-tx) inside the output, and over o, of
+ *                                    gy[b,iy-ty,ix-tx,o] * w[o,c,ty,tx]: a gather, every element of gx is written once.
+ *   ippm_conv4x4_bf16_grad_weight    gw[o,c,ty,tx] = sum over b,oy,ox of gy[b,oy,ox,o] * x[b,oy+ty,ox+tx,c]: per-chunk partial sums in the
+ *                                    scratch, added in chunk order by a second kernel.
+ * -1 with ippm_last_error set for a null pointer, batch outside [1, 2^24], ih or iw outside [4, 11], a scratch or tensor that is not
+ * 16-byte aligned; nothing is launched then.  No context needed, no host synchronisation, no allocation, launches on `stream` only. */
+#define IPPM_CONV4X4_WGRAD_CHUNK 256
+int ippm_conv4x4_bf16_scratch_bytes(int64_t batch, int32_t ih, int32_t iw, int64_t* bytes);
+int ippm_conv4x4_bf16_forward(const float* x, const float* w, int64_t batch, int32_t ih, int32_t iw, void* scratch, float* y, void* stream);
+int ippm_conv4x4_bf16_grad_input(const float* gy, const float* w, int64_t batch, int32_t ih, int32_t iw, void* scratch, float* gx,
+                                 void* stream);
+int ippm_conv4x4_bf16_grad_weight(const float* gy, const float* x, int64_t batch, int32_t ih, int32_t iw, void* scratch, float* gw,
+                                  void* stream);
+
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
  * Q(s_t)[a_t] -> td_target, discounted_return float. */

@@ -104,6 +104,25 @@ struct LayerGeom {
 
 constexpr int LT_M = 128, LT_N = 128, LT_K = 64, LT_LD = LT_K + 8;
 
+// One K step of a wavefront's 64 x 64 share of the tile: acc[n tile][m tile] += Ws[wn ..][k] * As[wm ..][k] over the LT_K k staged in LDS
+// (rows of LT_LD elements; fr = lane & 15, fk = (lane >> 4) * 8).  Shared with the training convolution (conv4x4_train.hip).
+__device__ __forceinline__ void lt_mma_step(const uint16_t* As, const uint16_t* Ws, int wm, int wn, int fr, int fk, floatx4 (&acc)[4][4]) {
+#pragma unroll
+  for (int kk = 0; kk < LT_K; kk += 32) {
+    bf16x8 af[4], wf[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      af[t] = *reinterpret_cast<const bf16x8*>(&As[(wm + t * 16 + fr) * LT_LD + kk + fk]);
+      wf[t] = *reinterpret_cast<const bf16x8*>(&Ws[(wn + t * 16 + fr) * LT_LD + kk + fk]);
+    }
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+        acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
+  }
+}
+
 // FIRST: the layer reads the float32 network input [B,11,11,PLANES] (5x5 kernel) and rounds it to bf16 on the way into LDS; otherwise
 // the bf16 activation of the layer before (PLANES is not used).
 template <bool FIRST, int PLANES = 0>
@@ -183,20 +202,7 @@ k_actor_layer(const void* __restrict__ in_, const uint16_t* __restrict__ w, cons
     stage();
     __syncthreads();
     load(k0 + LT_K < g.K ? k0 + LT_K : k0);   // (the last step re-reads its own tile: no branch around the loads)
-#pragma unroll
-    for (int kk = 0; kk < LT_K; kk += 32) {
-      bf16x8 af[4], wf[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        af[t] = *reinterpret_cast<const bf16x8*>(&As[(wm + t * 16 + fr) * LT_LD + kk + fk]);
-        wf[t] = *reinterpret_cast<const bf16x8*>(&Ws[(wn + t * 16 + fr) * LT_LD + kk + fk]);
-      }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-          acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
-    }
+    lt_mma_step(As, Ws, wm, wn, fr, fk, acc);
   }
 
   // D[n][m]: lane holds m = lane & 15 and n = (lane >> 4) * 4 + reg

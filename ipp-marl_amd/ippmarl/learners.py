@@ -11,6 +11,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _ffi
+from .networks import conv2_update as conv2_update_mode, resolve_conv2_update
 
 
 def _adam(parameters, lr: float, capturable: bool):
@@ -23,8 +24,10 @@ def _adam(parameters, lr: float, capturable: bool):
 
 
 class CriticLearner:
-    def __init__(self, params: Dict, critic, device, capturable: bool = False):
+    def __init__(self, params: Dict, critic, device, capturable: bool = False, conv2_update: str = "float32"):
         self.params = params
+        # conv2 of the forward-with-gradient pass and its gradients: "float32", or "bf16" (networks._Conv4x4Bf16); this learner's own
+        self.conv2_update = resolve_conv2_update(conv2_update)
         self.critic = critic.to(device)
         self.device = device
         self.target_critic = copy.deepcopy(critic).to(device)
@@ -56,7 +59,8 @@ class CriticLearner:
     def backward(self, states: torch.Tensor, actions: torch.Tensor, td_targets: torch.Tensor):
         """First half of a minibatch step: MSE on the chosen Q and its gradients (critic/learner.py:76-92).  The gradients
         are cleared in place, so views handed out by parallel.GradAllReducer.attach stay valid."""
-        q, _ = self.critic(states)
+        with conv2_update_mode(self.conv2_update):
+            q, _ = self.critic(states)
         q_chosen = q.gather(1, actions.long().view(-1, 1))
         loss = torch.square(q_chosen - td_targets.view(-1, 1).detach()).squeeze().mean()
         self.optimizer.zero_grad(set_to_none=False)
@@ -89,8 +93,10 @@ class CriticLearner:
 
 
 class ActorLearner:
-    def __init__(self, params: Dict, actor, device, ctx: Optional[_ffi.Context] = None, capturable: bool = False):
+    def __init__(self, params: Dict, actor, device, ctx: Optional[_ffi.Context] = None, capturable: bool = False,
+                 conv2_update: str = "float32"):
         self.params = params
+        self.conv2_update = resolve_conv2_update(conv2_update)   # as CriticLearner's
         self.actor = actor.to(device)
         self.device = device
         self.ctx = ctx
@@ -120,7 +126,8 @@ class ActorLearner:
     def backward(self, observations: torch.Tensor, actions: torch.Tensor, masks: torch.Tensor, q_values: torch.Tensor, eps: float):
         """First half of a minibatch step (actor/learner.py:52-97): loss and gradients.  The reference's loss broadcasts
         [B,1]*[B,1]*[B,A] before the mean, i.e. every sample is weighted by (#valid actions)/A."""
-        probs, hidden = self.actor(observations, eps)
+        with conv2_update_mode(self.conv2_update):
+            probs, hidden = self.actor(observations, eps)
         log_probs = torch.log(probs)
         adv = self.advantage(probs, q_values, masks, actions)
         log_chosen = log_probs.gather(1, actions.long().view(-1, 1)).squeeze(1)

@@ -8,8 +8,11 @@ critic/network.py:12-47) so that a reference ``state_dict`` / ``best_model.pth``
 """
 from __future__ import annotations
 
+import contextlib
+import contextvars
+import ctypes
 import os
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 from torch import nn
@@ -27,6 +30,35 @@ CONV3_AS_GEMM = os.environ.get("IPPMARL_CONV3_GEMM", "1") != "0"
 FUSED_BIAS_RELU = os.environ.get("IPPMARL_FUSED_BIAS_RELU", "1") != "0"
 # conv2's input gradient as GEMM + col2im (see _ConvDataGradAsGemm); IPPMARL_CONV2_BWD_GEMM=0 keeps the library's kernel
 CONV2_BWD_DATA_AS_GEMM = os.environ.get("IPPMARL_CONV2_BWD_GEMM", "1") != "0"
+
+
+# conv2 of a forward-with-gradient pass: "float32" (the library's convolution, the default) or "bf16" (libippmarl's matrix-core kernels,
+# see _Conv4x4Bf16).  The mode belongs to the CALLER of the forward -- a learner enters conv2_update(mode) around it -- and is neither
+# process-global nor stored in the module: whole-module pickles are the checkpoint format.
+CONV2_UPDATE_MODES = ("float32", "bf16")
+CONV2_UPDATE_ENV = "IPPMARL_CONV2_UPDATE"
+_CONV2_UPDATE: "contextvars.ContextVar[str]" = contextvars.ContextVar("ippmarl_conv2_update", default="float32")
+
+
+def resolve_conv2_update(conv2_update: Optional[str] = None) -> str:
+    """The update's conv2 path: the argument, else IPPMARL_CONV2_UPDATE, else "float32"; anything but "float32" / "bf16" raises."""
+    mode = conv2_update if conv2_update is not None else os.environ.get(CONV2_UPDATE_ENV, "") or "float32"
+    if mode not in CONV2_UPDATE_MODES:
+        raise ValueError(f"conv2 update must be one of {CONV2_UPDATE_MODES}, got {mode!r}")
+    return mode
+
+
+@contextlib.contextmanager
+def conv2_update(mode: str):
+    """Forwards with gradients run inside this block take ``mode`` for conv2 ("bf16" only where _Conv4x4Bf16.usable says so: device
+    float32 channels-last tensors under grad mode; everything else silently keeps the float32 path)."""
+    if mode not in CONV2_UPDATE_MODES:
+        raise ValueError(f"conv2 update must be one of {CONV2_UPDATE_MODES}, got {mode!r}")
+    token = _CONV2_UPDATE.set(mode)
+    try:
+        yield
+    finally:
+        _CONV2_UPDATE.reset(token)
 
 
 def epsilon_schedule(params: Dict, num_episode: int) -> float:
@@ -97,6 +129,54 @@ class _ConvDataGradAsGemm(torch.autograd.Function):
         return grad_x, grad_w, grad_b
 
 
+class _Conv4x4Bf16(torch.autograd.Function):
+    """Bias-free conv2 (4x4, 256 -> 256 channels, stride 1, no padding) whose forward, input gradient and weight gradient run on the
+    bf16 matrix cores (libippmarl's ippm_conv4x4_bf16_*, csrc/conv4x4_train.hip) instead of the library's float32 convolution.
+    Contract: x, weight and grad_out are rounded to bf16 on their way in, products accumulate in float32, outputs
+    are float32; deterministic, no atomics.  Tensors are logical NCHW over channels-last storage, as everywhere in the trunk.  No host
+    synchronisation; the scratch is allocated per call, so the calls record into a hipGraph like the rest of the round."""
+
+    @staticmethod
+    def usable(x: torch.Tensor, weight: torch.Tensor) -> bool:
+        return (torch.is_grad_enabled() and weight.requires_grad and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                and x.shape[0] >= 1 and tuple(weight.shape) == (256, 256, 4, 4) and x.shape[1] == 256 and weight.dtype == torch.float32
+                and weight.device == x.device and 4 <= x.shape[2] <= 11 and 4 <= x.shape[3] <= 11 and not x.is_sparse
+                and x.is_contiguous(memory_format=torch.channels_last))
+
+    @staticmethod
+    def _call(name: str, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, batch: int, ih: int, iw: int, partials: bool):
+        from . import _ffi
+        lib = _ffi.load_library()
+        nbytes = ctypes.c_int64(0)
+        # (forward and input gradient use the weight packs at the head of the scratch only: the size of a one-sample call)
+        _ffi.check(lib.ippm_conv4x4_bf16_scratch_bytes(batch if partials else 1, ih, iw, ctypes.addressof(nbytes)), "ippm_conv4x4_bf16_scratch_bytes")
+        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=out.device)
+        _ffi.check(getattr(lib, name)(a.data_ptr(), b.data_ptr(), batch, ih, iw, scratch.data_ptr(), out.data_ptr(),
+                                      torch.cuda.current_stream(out.device).cuda_stream), name)
+        return out
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        xs, w = x.contiguous(memory_format=torch.channels_last), weight.contiguous()
+        B, _, ih, iw = xs.shape
+        y = torch.empty((B, 256, ih - 3, iw - 3), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        return _Conv4x4Bf16._call("ippm_conv4x4_bf16_forward", xs, w, y, B, ih, iw, False)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors
+        xs, w = x.contiguous(memory_format=torch.channels_last), weight.contiguous()
+        g = grad_out.contiguous(memory_format=torch.channels_last)
+        B, _, ih, iw = xs.shape
+        grad_x = grad_w = None
+        if ctx.needs_input_grad[1]:
+            grad_w = _Conv4x4Bf16._call("ippm_conv4x4_bf16_grad_weight", g, xs, torch.empty_like(w), B, ih, iw, True)
+        if ctx.needs_input_grad[0]:
+            grad_x = _Conv4x4Bf16._call("ippm_conv4x4_bf16_grad_input", g, w, torch.empty_like(xs), B, ih, iw, False)
+        return grad_x, grad_w
+
+
 class _BiasReLU(torch.autograd.Function):
     """relu(x + bias) for a channels-last activation tensor as ONE pass in each direction (libippmarl's ippm_bias_relu_nhwc
     / ippm_bias_relu_backward_nhwc) instead of the bias pass + ReLU pass (and threshold pass + column reduction) PyTorch runs
@@ -149,13 +229,17 @@ class _ConvTrunk(nn.Module):
         self.fc2 = nn.Linear(256, 256)  # never used in forward (reference: commented out) -> never gets a gradient
         self.fc3 = nn.Linear(256, n_actions)
 
-    def _conv_relu(self, conv: nn.Conv2d, x: torch.Tensor, data_grad_as_gemm: bool):
-        """activation(conv(x)); on the device the convolution runs bias-free and bias + ReLU are one in-place pass."""
+    def _conv_relu(self, conv: nn.Conv2d, x: torch.Tensor, data_grad_as_gemm: bool, bf16_update: bool = False):
+        """activation(conv(x)); on the device the convolution runs bias-free and bias + ReLU are one in-place pass.  ``bf16_update``:
+        the bias-free convolution of a forward with gradients goes to _Conv4x4Bf16 where that is usable."""
         # (both paths below, and _ConvDataGradAsGemm's backward, are written for the unpadded stride-1 layers of the reference)
         assert tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (0, 0) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
         conv2d = _ConvDataGradAsGemm.apply if data_grad_as_gemm else torch.nn.functional.conv2d
         if x.is_cuda and FUSED_BIAS_RELU:
-            out = conv2d(x, conv.weight, None)
+            if bf16_update and conv.bias is not None and _Conv4x4Bf16.usable(x, conv.weight):
+                out = _Conv4x4Bf16.apply(x, conv.weight)
+            else:
+                out = conv2d(x, conv.weight, None)
             if _BiasReLU.usable(out, conv.bias):
                 return _BiasReLU.apply(out, conv.bias)
             return self.activation(out + conv.bias.view(1, -1, 1, 1))
@@ -175,7 +259,7 @@ class _ConvTrunk(nn.Module):
             return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
         x = x.permute(0, 3, 1, 2)  # NHWC storage -> logical NCHW (channels_last strides, no copy)
         h = self._conv_relu(self.conv1, x, False)
-        h = self._conv_relu(self.conv2, h, CONV2_BWD_DATA_AS_GEMM and h.requires_grad)
+        h = self._conv_relu(self.conv2, h, CONV2_BWD_DATA_AS_GEMM and h.requires_grad, _CONV2_UPDATE.get() == "bf16")
         if CONV3_AS_GEMM and h.shape[-2:] == self.conv3.kernel_size:
             # conv3 sees a 4x4 map with a 4x4 kernel: ONE output position, i.e. a plain [B, 4096] x [4096, 256] product.
             # As a GEMM it goes to hipBLASLt instead of an implicit-GEMM convolution with a degenerate output tile.
