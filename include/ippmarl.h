@@ -488,6 +488,31 @@ int ippm_conv4x4_bf16_grad_input(const float* gy, const float* w, int64_t batch,
 int ippm_conv4x4_bf16_grad_weight(const float* gy, const float* x, int64_t batch, int32_t ih, int32_t iw, void* scratch, float* gw,
                                   void* stream);
 
+/* ---- conv1 of the COMA update on the bf16 matrix cores (csrc/conv5x5_train.hip): the stride-1, unpadded 5x5 convolution from `planes`
+ * (7: actor, 12: critic) input planes of an 11x11 map to 256 channels of a 7x7 map, over channels-last float32 tensors: x [B,11,11,planes],
+ * y and gy [B,7,7,256]; w and gw in PyTorch's [256,planes,5,5].  The contract of the 4x4 family above, word for word: every operand tensor
+ * (x, w, gy) is rounded to bf16 (nearest even) on its way into LDS, products accumulate in float32 on mfma_f32_16x16x32_bf16, outputs are
+ * float32 and not rounded again.  K = 25 * planes is zero-padded to a multiple of 64 (175 -> 192, 300 -> 320); the padded columns are
+ * zeros, never memory.  Deterministic: no float atomics, every output element has one owner and a fixed summation order; a sample's
+ * forward does not depend on the batch around it, the weight gradient depends on the inputs and the batch size only (not on the device,
+ * the grid or the scratch's previous content).  No input gradient: the layer's input is data.
+ *   ippm_conv5x5_bf16_scratch_bytes  size of the caller-owned scratch for `batch`: the bf16 weight pack (256 x padded K), then the weight
+ *                                    gradient's float32 partial sums (256 x padded K per chunk of IPPM_CONV5X5_WGRAD_CHUNK samples).  The
+ *                                    forward uses the pack only.  Needs no initialisation; every call writes what it reads.
+ *   ippm_conv5x5_bf16_forward        y[b,oy,ox,o] = sum over ty,tx,c of x[b,oy+ty,ox+tx,c] * w[o,c,ty,tx]; with `bias` (float [256])
+ *                                    non-null, y = max(that + bias[o], 0) at the store: the float32 bits of ippm_bias_relu_nhwc run
+ *                                    on the bias-free output.
+ *   ippm_conv5x5_bf16_grad_weight    gw[o,c,ty,tx] = sum over b,oy,ox of gy[b,oy,ox,o] * x[b,oy+ty,ox+tx,c]: per-chunk partial sums in the
+ *                                    scratch, added in chunk order by a second kernel.
+ * -1 with ippm_last_error set for a null pointer (but `bias`), batch outside [1, 2^24], planes other than 7 or 12, a scratch or tensor
+ * that is not 16-byte aligned; nothing is launched then.  No context needed, no host synchronisation, no allocation, launches on
+ * `stream` only. */
+#define IPPM_CONV5X5_WGRAD_CHUNK 64
+int ippm_conv5x5_bf16_scratch_bytes(int64_t batch, int32_t planes, int64_t* bytes);
+int ippm_conv5x5_bf16_forward(const float* x, const float* w, const float* bias, int64_t batch, int32_t planes, void* scratch, float* y,
+                              void* stream);
+int ippm_conv5x5_bf16_grad_weight(const float* gy, const float* x, int64_t batch, int32_t planes, void* scratch, float* gw, void* stream);
+
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
  * Q(s_t)[a_t] -> td_target, discounted_return float. */

@@ -19,6 +19,7 @@ FAULT_WORK_OVERFLOW = 0x40000000   # IPPM_FAULT_WORK_OVERFLOW (ippmarl.h): stick
 FEAT, ACTOR_PLANES, CRITIC_PLANES = 11, 7, 12
 STEP_COMM, STEP_GLOBAL, STEP_MOVE, STEP_TILES = 1, 2, 4, 8   # ippm_plan_step flags
 CONV4X4_WGRAD_CHUNK = 256   # samples per partial sum of ippm_conv4x4_bf16_grad_weight (IPPM_CONV4X4_WGRAD_CHUNK)
+CONV5X5_WGRAD_CHUNK = 64   # samples per partial sum of ippm_conv5x5_bf16_grad_weight (IPPM_CONV5X5_WGRAD_CHUNK)
 SENSE_REC_WORDS = 8   # words per agent of ippm_plan_step's rect_next / ippm_sense_step's rect_in (IPPM_SENSE_REC_WORDS)
 # kernel classes of ippm_read_kernel_times (IPPM_T_*)
 TIMED = {"sense": 0, "fuse": 1, "plan": 2, "actor_features": 3, "critic_features": 4, "reset": 5, "terrain": 6, "reset_maps": 7,
@@ -115,6 +116,9 @@ PROTOTYPES = {
     "ippm_conv4x4_bf16_forward": [P, P, I64, I32, I32, P, P, P],
     "ippm_conv4x4_bf16_grad_input": [P, P, I64, I32, I32, P, P, P],
     "ippm_conv4x4_bf16_grad_weight": [P, P, I64, I32, I32, P, P, P],
+    "ippm_conv5x5_bf16_scratch_bytes": [I64, I32, P],
+    "ippm_conv5x5_bf16_forward": [P, P, P, I64, I32, P, P, P],
+    "ippm_conv5x5_bf16_grad_weight": [P, P, I64, I32, P, P, P],
     "ippm_ig_candidates": [P, P, P, P, P, I32, P],
     "ippm_ig_select": [P, P, P, P, I32, P, P, I32, P],
     "ippm_f1_counts": [P, P, P, I32, C.c_float, P, I32, P],

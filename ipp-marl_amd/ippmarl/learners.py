@@ -12,6 +12,7 @@ import torch
 
 from . import _ffi
 from .networks import conv2_update as conv2_update_mode, resolve_conv2_update
+from .networks import resolve_trunk_update, trunk_update as trunk_update_mode
 
 
 def _adam(parameters, lr: float, capturable: bool):
@@ -24,8 +25,11 @@ def _adam(parameters, lr: float, capturable: bool):
 
 
 class CriticLearner:
-    def __init__(self, params: Dict, critic, device, capturable: bool = False, conv2_update: str = "float32"):
+    def __init__(self, params: Dict, critic, device, capturable: bool = False, conv2_update: str = "float32",
+                 trunk_update: str = "float32"):
         self.params = params
+        # conv1, conv2 and conv3 of the same pass: "float32", or "bf16" (networks.trunk_update; implies the bf16 conv2)
+        self.trunk_update = resolve_trunk_update(trunk_update)
         # conv2 of the forward-with-gradient pass and its gradients: "float32", or "bf16" (networks._Conv4x4Bf16); this learner's own
         self.conv2_update = resolve_conv2_update(conv2_update)
         self.critic = critic.to(device)
@@ -59,7 +63,7 @@ class CriticLearner:
     def backward(self, states: torch.Tensor, actions: torch.Tensor, td_targets: torch.Tensor):
         """First half of a minibatch step: MSE on the chosen Q and its gradients (critic/learner.py:76-92).  The gradients
         are cleared in place, so views handed out by parallel.GradAllReducer.attach stay valid."""
-        with conv2_update_mode(self.conv2_update):
+        with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update):
             q, _ = self.critic(states)
         q_chosen = q.gather(1, actions.long().view(-1, 1))
         loss = torch.square(q_chosen - td_targets.view(-1, 1).detach()).squeeze().mean()
@@ -94,9 +98,10 @@ class CriticLearner:
 
 class ActorLearner:
     def __init__(self, params: Dict, actor, device, ctx: Optional[_ffi.Context] = None, capturable: bool = False,
-                 conv2_update: str = "float32"):
+                 conv2_update: str = "float32", trunk_update: str = "float32"):
         self.params = params
         self.conv2_update = resolve_conv2_update(conv2_update)   # as CriticLearner's
+        self.trunk_update = resolve_trunk_update(trunk_update)
         self.actor = actor.to(device)
         self.device = device
         self.ctx = ctx
@@ -126,7 +131,7 @@ class ActorLearner:
     def backward(self, observations: torch.Tensor, actions: torch.Tensor, masks: torch.Tensor, q_values: torch.Tensor, eps: float):
         """First half of a minibatch step (actor/learner.py:52-97): loss and gradients.  The reference's loss broadcasts
         [B,1]*[B,1]*[B,A] before the mean, i.e. every sample is weighted by (#valid actions)/A."""
-        with conv2_update_mode(self.conv2_update):
+        with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update):
             probs, hidden = self.actor(observations, eps)
         log_probs = torch.log(probs)
         adv = self.advantage(probs, q_values, masks, actions)

@@ -61,6 +61,35 @@ def conv2_update(mode: str):
         _CONV2_UPDATE.reset(token)
 
 
+# conv1, conv2 and conv3 of a forward-with-gradient pass: "float32" (the default: whatever conv2_update says for conv2, the float32
+# library for the rest) or "bf16" (conv1 through _Conv5x5Bf16, conv2 through _Conv4x4Bf16 whatever conv2_update says, conv3 through
+# _Conv3Bf16).  The rules of the conv2 switch: the mode belongs to the caller of the forward and is never stored in the module.
+TRUNK_UPDATE_MODES = ("float32", "bf16")
+TRUNK_UPDATE_ENV = "IPPMARL_TRUNK_UPDATE"
+_TRUNK_UPDATE: "contextvars.ContextVar[str]" = contextvars.ContextVar("ippmarl_trunk_update", default="float32")
+
+
+def resolve_trunk_update(trunk_update: Optional[str] = None) -> str:
+    """The update's trunk path: the argument, else IPPMARL_TRUNK_UPDATE, else "float32"; anything but "float32" / "bf16" raises."""
+    mode = trunk_update if trunk_update is not None else os.environ.get(TRUNK_UPDATE_ENV, "") or "float32"
+    if mode not in TRUNK_UPDATE_MODES:
+        raise ValueError(f"trunk update must be one of {TRUNK_UPDATE_MODES}, got {mode!r}")
+    return mode
+
+
+@contextlib.contextmanager
+def trunk_update(mode: str):
+    """Forwards with gradients run inside this block take ``mode`` for conv1, conv2 and conv3 ("bf16" only where the three Functions'
+    ``usable`` say so: device float32 channels-last tensors under grad mode; everything else silently keeps the float32 path)."""
+    if mode not in TRUNK_UPDATE_MODES:
+        raise ValueError(f"trunk update must be one of {TRUNK_UPDATE_MODES}, got {mode!r}")
+    token = _TRUNK_UPDATE.set(mode)
+    try:
+        yield
+    finally:
+        _TRUNK_UPDATE.reset(token)
+
+
 def epsilon_schedule(params: Dict, num_episode: int) -> float:
     """Linear anneal eps_max -> eps_min over eps_anneal_phase episodes (actor/network.py:53-58)."""
     m = params["experiment"]["missions"]
@@ -177,6 +206,106 @@ class _Conv4x4Bf16(torch.autograd.Function):
         return grad_x, grad_w
 
 
+class _Conv3Bf16(torch.autograd.Function):
+    """Bias-free conv3 under trunk_update("bf16"): a 4x4 kernel over a 4x4 map, one output position.  x is logical [B,256,4,4] over
+    channels-last storage, the result [B,256].  Forward and input gradient go through the 4x4 entry points of _Conv4x4Bf16 (ih = iw = 4),
+    which tools/trunk_update_ab.py measured 1.6 x and 2.3 x ahead of the default path's float32 GEMMs at config 3's minibatch; the weight
+    gradient (K = 256 rows per partial sum, 4 MiB of partial sums per 256 samples) only ties there and stays the float32 GEMM on the
+    unrounded operands (profiles/r12/README.md)."""
+
+    @staticmethod
+    def usable(x: torch.Tensor, weight: torch.Tensor) -> bool:
+        return _Conv4x4Bf16.usable(x, weight) and tuple(x.shape[2:]) == (4, 4)
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        xs, w = x.contiguous(memory_format=torch.channels_last), weight.contiguous()
+        B = xs.shape[0]
+        return _Conv4x4Bf16._call("ippm_conv4x4_bf16_forward", xs, w, torch.empty((B, 256), dtype=x.dtype, device=x.device), B, 4, 4, False)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors
+        xs, w = x.contiguous(memory_format=torch.channels_last), weight.contiguous()
+        g = grad_out.contiguous()                                                       # [B,256]
+        B = xs.shape[0]
+        grad_x = grad_w = None
+        if ctx.needs_input_grad[1]:
+            # [256, (ty, tx, c)] from the channels-last activation flattened as a view, then PyTorch's [256,256,4,4]
+            grad_w = (g.t() @ xs.permute(0, 2, 3, 1).reshape(B, -1)).view(256, 4, 4, 256).permute(0, 3, 1, 2).contiguous()
+        if ctx.needs_input_grad[0]:
+            grad_x = _Conv4x4Bf16._call("ippm_conv4x4_bf16_grad_input", g, w, torch.empty_like(xs), B, 4, 4, False)
+        return grad_x, grad_w
+
+
+class _Conv5x5Bf16(torch.autograd.Function):
+    """relu(conv1(x) + bias) (5x5, 7 or 12 planes -> 256 channels, 11x11 -> 7x7) whose forward -- bias and ReLU fused into its store -- and
+    weight gradient run on the bf16 matrix cores (libippmarl's ippm_conv5x5_bf16_*, csrc/conv5x5_train.hip).  Contract (DESIGN.md section
+    7): x, weight and the gradient behind the ReLU are rounded to bf16 on their way in, products accumulate in float32, outputs are
+    float32; deterministic, no atomics.  The backward is ippm_bias_relu_backward_nhwc on the saved output (the gradient through the ReLU,
+    the bias gradient), then the weight gradient; the input is data and gets none.  No host synchronisation; the scratch is allocated per
+    call, so the calls record into a hipGraph like the rest of the round."""
+
+    @staticmethod
+    def usable(x: torch.Tensor, weight: torch.Tensor, bias) -> bool:
+        return (FUSED_BIAS_RELU and torch.is_grad_enabled() and weight.requires_grad and bias is not None and x.is_cuda
+                and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1 and x.shape[1] in (7, 12)
+                and tuple(x.shape[2:]) == (11, 11) and tuple(weight.shape) == (256, x.shape[1], 5, 5) and weight.dtype == torch.float32
+                and bias.dtype == torch.float32 and weight.device == x.device and bias.device == x.device and not x.is_sparse
+                and not x.requires_grad and x.is_contiguous(memory_format=torch.channels_last))
+
+    @staticmethod
+    def _scratch(lib, batch: int, planes: int, device):
+        from . import _ffi
+        nbytes = ctypes.c_int64(0)
+        _ffi.check(lib.ippm_conv5x5_bf16_scratch_bytes(batch, planes, ctypes.addressof(nbytes)), "ippm_conv5x5_bf16_scratch_bytes")
+        return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from . import _ffi
+        lib = _ffi.load_library()
+        xs, w, b = x.contiguous(memory_format=torch.channels_last), weight.detach().contiguous(), bias.detach().contiguous()
+        if xs.data_ptr() % 16:                            # (a view into a larger buffer: a sample is 847 or 1452 floats)
+            xs = xs.clone(memory_format=torch.channels_last)
+        B, planes = xs.shape[0], xs.shape[1]
+        y = torch.empty((B, 256, 7, 7), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        # (the forward uses the weight pack at the head of the scratch only: the size of a one-sample call minus its partial sums)
+        scratch = _Conv5x5Bf16._scratch(lib, 1, planes, x.device)
+        _ffi.check(lib.ippm_conv5x5_bf16_forward(xs.data_ptr(), w.data_ptr(), b.data_ptr(), B, planes, scratch.data_ptr(), y.data_ptr(),
+                                                 torch.cuda.current_stream(x.device).cuda_stream), "ippm_conv5x5_bf16_forward")
+        ctx.save_for_backward(xs, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        from . import _ffi
+        xs, y = ctx.saved_tensors
+        lib, stream = _ffi.load_library(), torch.cuda.current_stream(y.device).cuda_stream
+        B, planes = xs.shape[0], xs.shape[1]
+        g = grad_y.contiguous(memory_format=torch.channels_last)
+        grad_pre = torch.empty_like(y)                    # channels-last like y
+        grad_b = torch.zeros(256, dtype=y.dtype, device=y.device)
+        _ffi.check(lib.ippm_bias_relu_backward_nhwc(g.data_ptr(), y.data_ptr(), grad_pre.data_ptr(), _ffi.ptr(grad_b), B * 49, 256, stream),
+                   "ippm_bias_relu_backward_nhwc")
+        grad_w = _Conv5x5Bf16.grad_weight(grad_pre, xs) if ctx.needs_input_grad[1] else None
+        return None, grad_w, (grad_b if ctx.needs_input_grad[2] else None)
+
+    @staticmethod
+    def grad_weight(grad_pre: torch.Tensor, xs: torch.Tensor) -> torch.Tensor:
+        """The weight gradient [256,planes,5,5] of the bias-free convolution at the channels-last input ``xs`` for the output gradient
+        ``grad_pre`` (channels-last, 16-byte aligned both)."""
+        from . import _ffi
+        lib = _ffi.load_library()
+        B, planes = xs.shape[0], xs.shape[1]
+        grad_w = torch.empty((256, planes, 5, 5), dtype=xs.dtype, device=xs.device)
+        scratch = _Conv5x5Bf16._scratch(lib, B, planes, xs.device)
+        _ffi.check(lib.ippm_conv5x5_bf16_grad_weight(grad_pre.data_ptr(), xs.data_ptr(), B, planes, scratch.data_ptr(), grad_w.data_ptr(),
+                                                     torch.cuda.current_stream(xs.device).cuda_stream), "ippm_conv5x5_bf16_grad_weight")
+        return grad_w
+
+
 class _BiasReLU(torch.autograd.Function):
     """relu(x + bias) for a channels-last activation tensor as ONE pass in each direction (libippmarl's ippm_bias_relu_nhwc
     / ippm_bias_relu_backward_nhwc) instead of the bias pass + ReLU pass (and threshold pass + column reduction) PyTorch runs
@@ -258,9 +387,15 @@ class _ConvTrunk(nn.Module):
             parts = [self.trunk(x[lo:lo + self.MAX_SAMPLES]) for lo in range(0, x.shape[0], self.MAX_SAMPLES)]
             return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
         x = x.permute(0, 3, 1, 2)  # NHWC storage -> logical NCHW (channels_last strides, no copy)
-        h = self._conv_relu(self.conv1, x, False)
-        h = self._conv_relu(self.conv2, h, CONV2_BWD_DATA_AS_GEMM and h.requires_grad, _CONV2_UPDATE.get() == "bf16")
-        if CONV3_AS_GEMM and h.shape[-2:] == self.conv3.kernel_size:
+        bf16_trunk = _TRUNK_UPDATE.get() == "bf16"
+        if bf16_trunk and _Conv5x5Bf16.usable(x, self.conv1.weight, self.conv1.bias):
+            h = _Conv5x5Bf16.apply(x, self.conv1.weight, self.conv1.bias)
+        else:
+            h = self._conv_relu(self.conv1, x, False)
+        h = self._conv_relu(self.conv2, h, CONV2_BWD_DATA_AS_GEMM and h.requires_grad, bf16_trunk or _CONV2_UPDATE.get() == "bf16")
+        if bf16_trunk and h.is_cuda and FUSED_BIAS_RELU and self.conv3.bias is not None and _Conv3Bf16.usable(h, self.conv3.weight):
+            h = self.activation(_Conv3Bf16.apply(h, self.conv3.weight) + self.conv3.bias)
+        elif CONV3_AS_GEMM and h.shape[-2:] == self.conv3.kernel_size:
             # conv3 sees a 4x4 map with a 4x4 kernel: ONE output position, i.e. a plain [B, 4096] x [4096, 256] product.
             # As a GEMM it goes to hipBLASLt instead of an implicit-GEMM convolution with a degenerate output tile.
             # (h is channels-last: flattening it in (H, W, C) order is a view; the weight is permuted to match.)
