@@ -513,6 +513,49 @@ int ippm_conv5x5_bf16_forward(const float* x, const float* w, const float* bias,
                               void* stream);
 int ippm_conv5x5_bf16_grad_weight(const float* gy, const float* x, int64_t batch, int32_t planes, void* scratch, float* gw, void* stream);
 
+/* ---- the heads of the COMA update (csrc/head_train.hip): everything behind conv3 in a learner's forward-with-gradient pass -- fc1, ReLU,
+ * fc3 (actor/network.py:81-88, critic/network.py:42-47), the loss (critic/learner.py:76-92; actor/learner.py:52-97) and the
+ * gradients back to conv3's output h [batch,256] -- over float32 tensors in PyTorch's layouts: fc1_w [256,256], fc1_b [256], fc3_w
+ * [n_actions,256], fc3_b [n_actions], n_actions in [1, 32]; a1, gh [batch,256]; logits, q, dlogits, probs [batch,n_actions].
+ * Numerical contract, the 4x4 family's extended: both operands of the six products z1 = h W1^T, logits = a1 W3^T, ga1 = dlogits W3,
+ * gh = gz1 W1, gW1 = gz1^T h, gW3 = dlogits^T a1 are rounded to bf16 (nearest even) on their way in, products accumulate in float32 on
+ * mfma_f32_16x16x32_bf16, outputs are float32 and not rounded again.  Everything else is float32 on unrounded values: the bias adds,
+ * a1 = relu(z1 + b1) with the NaN-passing ReLU of ippm_bias_relu_nhwc, gz1 = ga1 [a1 > 0], gb1 = sum_b gz1, gb3 = sum_b dlogits and the
+ * losses' per-row arithmetic (the ONE sum over the batch that makes a loss is carried in double and rounded to float32 once).  Deterministic: no float atomics, every output element has one owner and a fixed summation order; a sample's a1, logits,
+ * dlogits (times batch) and gh are the same bits alone and in any batch; the sums over the batch (gW1, gb1, gW3, gb3, the losses) are
+ * per-chunk partial sums of IPPM_HEAD_WGRAD_CHUNK samples in the scratch, added in chunk order by a second kernel: they depend on the
+ * inputs and the batch size only (not on the device, the grid or the scratch's previous content).
+ *   ippm_head_scratch_bytes  size of the caller-owned scratch for `batch`: the losses' partial sums (a double per chunk, rounded up to 16
+ *                            bytes: all the two loss entry points use), gz1 [batch,256], the gradients' partial sums (296 064 bytes per
+ *                            chunk).  Needs no initialisation.
+ *   ippm_head_forward        a1 = relu(h W1^T + b1), logits = a1 W3^T + b3: one kernel.  Uses no scratch (NULL is accepted).
+ *   ippm_critic_loss         loss = mean_b (q[b,a_b] - td_b)^2 (float [1]); q_chosen[b] = q[b,a_b]; dq[b,a] = 2 (q[b,a_b] - td_b) / batch
+ *                            at a = a_b and 0 elsewhere.  action int32 [batch]; one outside [0, n_actions) gives NaN in its row and in
+ *                            the loss and reads nothing out of range.
+ *   ippm_actor_loss          with s = softmax(logits) (the maximum subtracted, as ippm_actor_forward), p = (1 - eps) s + eps / n_actions
+ *                            (eps_dev, a device float, wins over eps when non-NULL): adv = ippm_coma_advantage's arithmetic on (p, q_values,
+ *                            mask, action), bit for bit; w_b = sum_a mask[b,a] / n_actions; loss = -mean_b adv_b log p[b,a_b] w_b;
+ *                            dlogits[b,a] = -(adv_b w_b / batch) (1 - eps) s[b,c] ([a == c] - s[b,a]) / p[b,c], c = a_b (adv is not
+ *                            differentiated).  mask uint8 [batch,n_actions]; probs (p) may be NULL.
+ *   ippm_head_backward       from dlogits * scale (scale_dev: a device float, NULL = 1; the product is float32, before any rounding):
+ *                            gh [batch,256] and the gradients of fc1_w, fc1_b, fc3_w, fc3_b in the parameters' layouts.  a1 is
+ *                            ippm_head_forward's.
+ * -1 with ippm_last_error set for a null pointer (but the optional ones), batch outside [1, 2^24], n_actions outside [1, 32], a
+ * scratch, h, a1, gh, fc1_w, fc1_b or fc3_w that is not 16-byte aligned; nothing is launched then.  No context needed, no host
+ * synchronisation, no allocation, launches on `stream` only. */
+#define IPPM_HEAD_WGRAD_CHUNK 64
+int ippm_head_scratch_bytes(int64_t batch, int32_t n_actions, int64_t* bytes);
+int ippm_head_forward(const float* h, const float* fc1_w, const float* fc1_b, const float* fc3_w, const float* fc3_b, int64_t batch,
+                      int32_t n_actions, void* scratch, float* a1, float* logits, void* stream);
+int ippm_critic_loss(const float* q, const int32_t* action, const float* td, int64_t batch, int32_t n_actions, void* scratch, float* loss,
+                     float* q_chosen, float* dq, void* stream);
+int ippm_actor_loss(const float* logits, const float* q_values, const uint8_t* mask, const int32_t* action, int64_t batch,
+                    int32_t n_actions, float eps, const float* eps_dev, void* scratch, float* loss, float* adv, float* probs,
+                    float* dlogits, void* stream);
+int ippm_head_backward(const float* dlogits, const float* scale_dev, const float* a1, const float* h, const float* fc1_w,
+                       const float* fc3_w, int64_t batch, int32_t n_actions, void* scratch, float* gh, float* g_fc1_w, float* g_fc1_b,
+                       float* g_fc3_w, float* g_fc3_b, void* stream);
+
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
  * Q(s_t)[a_t] -> td_target, discounted_return float. */

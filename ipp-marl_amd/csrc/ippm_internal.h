@@ -247,6 +247,23 @@ __device__ __forceinline__ float ippm_wave_sum(float v) {
   return v;
 }
 
+// K7's row (actor/learner.py:55-83), shared by k_coma_advantage (learn.hip) and the actor loss of the update's head (head_train.hip): one
+// 32-lane half-wave per row, lane = action.  prob, qv, m: the lane's pi, Q and mask (0 where !on).  pi~ = pi*mask / max(sum, 1e-5),
+// floored at 1e-5 -> pn; returns the baseline sum_a pi~(a) Q(a) mask(a) in every lane.
+__device__ __forceinline__ float ippm_coma_baseline(bool on, float prob, float qv, float m, float& pn) {
+  float p = on ? prob * m : 0.f;
+  float s = p;
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 32);
+  s = s < 1e-5f ? 1e-5f : s;
+  pn = p / s;
+  pn = pn <= 1e-5f ? 1e-5f : pn;
+  float b = on ? pn * qv * m : 0.f;
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) b += __shfl_xor(b, o, 32);
+  return b;
+}
+
 // Philox4x32-10 (Salmon et al., SC'11); mirrored in oracle/ipp_oracle.py::philox4x32
 struct Philox4 {
   uint32_t v[4];

@@ -15,16 +15,8 @@ k_coma_advantage(const float* __restrict__ probs, const float* __restrict__ q, c
   const bool on = lane < A;
   const float m = on ? (float)mask[(size_t)row * A + lane] : 0.f;
   const float qv = on ? q[(size_t)row * A + lane] : 0.f;
-  float p = on ? probs[(size_t)row * A + lane] * m : 0.f;
-  float s = p;
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 32);
-  s = s < 1e-5f ? 1e-5f : s;
-  float pn = p / s;
-  pn = pn <= 1e-5f ? 1e-5f : pn;
-  float b = on ? pn * qv * m : 0.f;
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) b += __shfl_xor(b, o, 32);
+  float pn;
+  const float b = ippm_coma_baseline(on, on ? probs[(size_t)row * A + lane] : 0.f, qv, m, pn);   // (the row's code: ippm_internal.h)
   if (pi_tilde && on) pi_tilde[(size_t)row * A + lane] = pn;
   if (lane == 0) adv[row] = q[(size_t)row * A + action[row]] - b;
 }

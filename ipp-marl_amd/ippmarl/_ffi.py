@@ -20,6 +20,7 @@ FEAT, ACTOR_PLANES, CRITIC_PLANES = 11, 7, 12
 STEP_COMM, STEP_GLOBAL, STEP_MOVE, STEP_TILES = 1, 2, 4, 8   # ippm_plan_step flags
 CONV4X4_WGRAD_CHUNK = 256   # samples per partial sum of ippm_conv4x4_bf16_grad_weight (IPPM_CONV4X4_WGRAD_CHUNK)
 CONV5X5_WGRAD_CHUNK = 64   # samples per partial sum of ippm_conv5x5_bf16_grad_weight (IPPM_CONV5X5_WGRAD_CHUNK)
+HEAD_WGRAD_CHUNK = 64   # samples per partial sum of ippm_head_backward and the two losses (IPPM_HEAD_WGRAD_CHUNK)
 SENSE_REC_WORDS = 8   # words per agent of ippm_plan_step's rect_next / ippm_sense_step's rect_in (IPPM_SENSE_REC_WORDS)
 # kernel classes of ippm_read_kernel_times (IPPM_T_*)
 TIMED = {"sense": 0, "fuse": 1, "plan": 2, "actor_features": 3, "critic_features": 4, "reset": 5, "terrain": 6, "reset_maps": 7,
@@ -119,6 +120,11 @@ PROTOTYPES = {
     "ippm_conv5x5_bf16_scratch_bytes": [I64, I32, P],
     "ippm_conv5x5_bf16_forward": [P, P, P, I64, I32, P, P, P],
     "ippm_conv5x5_bf16_grad_weight": [P, P, I64, I32, P, P, P],
+    "ippm_head_scratch_bytes": [I64, I32, P],
+    "ippm_head_forward": [P, P, P, P, P, I64, I32, P, P, P, P],
+    "ippm_critic_loss": [P, P, P, I64, I32, P, P, P, P, P],
+    "ippm_actor_loss": [P, P, P, P, I64, I32, C.c_float, P, P, P, P, P, P, P],
+    "ippm_head_backward": [P, P, P, P, P, P, I64, I32, P, P, P, P, P, P, P],
     "ippm_ig_candidates": [P, P, P, P, P, I32, P],
     "ippm_ig_select": [P, P, P, P, I32, P, P, I32, P],
     "ippm_f1_counts": [P, P, P, I32, C.c_float, P, I32, P],

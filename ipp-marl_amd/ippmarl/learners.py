@@ -13,6 +13,7 @@ import torch
 from . import _ffi
 from .networks import conv2_update as conv2_update_mode, resolve_conv2_update
 from .networks import resolve_trunk_update, trunk_update as trunk_update_mode
+from .networks import _ActorLossBf16, _CriticLossBf16, head_update as head_update_mode, resolve_head_update
 
 
 def _adam(parameters, lr: float, capturable: bool):
@@ -25,9 +26,11 @@ def _adam(parameters, lr: float, capturable: bool):
 
 
 class CriticLearner:
-    def __init__(self, params: Dict, critic, device, capturable: bool = False, conv2_update: str = "float32",
+    def __init__(self, params: Dict, critic, device, capturable: bool = False, head_update: str = "float32", conv2_update: str = "float32",
                  trunk_update: str = "float32"):
         self.params = params
+        # fc1, ReLU, fc3 and the loss of the same pass: "float32", or "bf16" (networks._HeadBf16, _CriticLossBf16); independent of the others
+        self.head_update = resolve_head_update(head_update)
         # conv1, conv2 and conv3 of the same pass: "float32", or "bf16" (networks.trunk_update; implies the bf16 conv2)
         self.trunk_update = resolve_trunk_update(trunk_update)
         # conv2 of the forward-with-gradient pass and its gradients: "float32", or "bf16" (networks._Conv4x4Bf16); this learner's own
@@ -63,10 +66,17 @@ class CriticLearner:
     def backward(self, states: torch.Tensor, actions: torch.Tensor, td_targets: torch.Tensor):
         """First half of a minibatch step: MSE on the chosen Q and its gradients (critic/learner.py:76-92).  The gradients
         are cleared in place, so views handed out by parallel.GradAllReducer.attach stay valid."""
-        with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update):
-            q, _ = self.critic(states)
-        q_chosen = q.gather(1, actions.long().view(-1, 1))
-        loss = torch.square(q_chosen - td_targets.view(-1, 1).detach()).squeeze().mean()
+        if self.head_update == "bf16" and not self.collect and states.is_cuda:
+            # the native head: fc1 .. fc3 in one kernel, the loss and its gradient in another (diagnostics keep the PyTorch head)
+            with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update), head_update_mode("bf16"):
+                q, _ = self.critic.trunk(states)
+            loss, q_chosen = _CriticLossBf16.apply(q, actions, td_targets)
+            q_chosen = q_chosen.view(-1, 1)
+        else:
+            with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update):
+                q, _ = self.critic(states)
+            q_chosen = q.gather(1, actions.long().view(-1, 1))
+            loss = torch.square(q_chosen - td_targets.view(-1, 1).detach()).squeeze().mean()
         self.optimizer.zero_grad(set_to_none=False)
         loss.backward()
         self._pending = (states, actions, td_targets, loss.detach(), q_chosen.detach())
@@ -98,8 +108,9 @@ class CriticLearner:
 
 class ActorLearner:
     def __init__(self, params: Dict, actor, device, ctx: Optional[_ffi.Context] = None, capturable: bool = False,
-                 conv2_update: str = "float32", trunk_update: str = "float32"):
+                 head_update: str = "float32", conv2_update: str = "float32", trunk_update: str = "float32"):
         self.params = params
+        self.head_update = resolve_head_update(head_update)     # as CriticLearner's (networks._HeadBf16, _ActorLossBf16)
         self.conv2_update = resolve_conv2_update(conv2_update)   # as CriticLearner's
         self.trunk_update = resolve_trunk_update(trunk_update)
         self.actor = actor.to(device)
@@ -131,6 +142,14 @@ class ActorLearner:
     def backward(self, observations: torch.Tensor, actions: torch.Tensor, masks: torch.Tensor, q_values: torch.Tensor, eps: float):
         """First half of a minibatch step (actor/learner.py:52-97): loss and gradients.  The reference's loss broadcasts
         [B,1]*[B,1]*[B,A] before the mean, i.e. every sample is weighted by (#valid actions)/A."""
+        if self.head_update == "bf16" and not self.collect and observations.is_cuda:
+            # the native head: the trunk's logits, then softmax, epsilon mix, K7, the loss and its gradient in one kernel
+            with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update), head_update_mode("bf16"):
+                logits, _ = self.actor.trunk(observations)
+            loss, adv = _ActorLossBf16.apply(logits, q_values, masks, actions, eps)
+            self.optimizer.zero_grad(set_to_none=False)
+            loss.backward()
+            return loss.detach(), adv
         with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update):
             probs, hidden = self.actor(observations, eps)
         log_probs = torch.log(probs)

@@ -90,6 +90,35 @@ def trunk_update(mode: str):
         _TRUNK_UPDATE.reset(token)
 
 
+# Everything behind conv3 of a forward-with-gradient pass -- fc1, ReLU, fc3 (and, in the learners, the loss): "float32" (the default:
+# PyTorch's GEMMs and elementwise passes) or "bf16" (libippmarl's head kernels, see _HeadBf16).  The rules of the other two switches:
+# the mode belongs to the caller of the forward and is never stored in the module.  Independent of conv2_update and trunk_update.
+HEAD_UPDATE_MODES = ("float32", "bf16")
+HEAD_UPDATE_ENV = "IPPMARL_HEAD_UPDATE"
+_HEAD_UPDATE: "contextvars.ContextVar[str]" = contextvars.ContextVar("ippmarl_head_update", default="float32")
+
+
+def resolve_head_update(head_update: Optional[str] = None) -> str:
+    """The update's head path: the argument, else IPPMARL_HEAD_UPDATE, else "float32"; anything but "float32" / "bf16" raises."""
+    mode = head_update if head_update is not None else os.environ.get(HEAD_UPDATE_ENV, "") or "float32"
+    if mode not in HEAD_UPDATE_MODES:
+        raise ValueError(f"head update must be one of {HEAD_UPDATE_MODES}, got {mode!r}")
+    return mode
+
+
+@contextlib.contextmanager
+def head_update(mode: str):
+    """Forwards with gradients run inside this block take ``mode`` for fc1, ReLU and fc3 ("bf16" only where _HeadBf16.usable says so:
+    device float32 contiguous tensors under grad mode; everything else silently keeps the float32 path)."""
+    if mode not in HEAD_UPDATE_MODES:
+        raise ValueError(f"head update must be one of {HEAD_UPDATE_MODES}, got {mode!r}")
+    token = _HEAD_UPDATE.set(mode)
+    try:
+        yield
+    finally:
+        _HEAD_UPDATE.reset(token)
+
+
 def epsilon_schedule(params: Dict, num_episode: int) -> float:
     """Linear anneal eps_max -> eps_min over eps_anneal_phase episodes (actor/network.py:53-58)."""
     m = params["experiment"]["missions"]
@@ -306,6 +335,119 @@ class _Conv5x5Bf16(torch.autograd.Function):
         return grad_w
 
 
+def _head_scratch(lib, batch: int, n_actions: int, device, losses_only: bool = False):
+    """The scratch of the head entry points for ``batch``; ``losses_only``: its first part, all that the two losses use (ippmarl.h)."""
+    from . import _ffi
+    if losses_only:
+        chunks = (batch + _ffi.HEAD_WGRAD_CHUNK - 1) // _ffi.HEAD_WGRAD_CHUNK
+        return torch.empty((chunks + 1) // 2 * 16, dtype=torch.uint8, device=device)
+    nbytes = ctypes.c_int64(0)
+    _ffi.check(lib.ippm_head_scratch_bytes(batch, n_actions, ctypes.addressof(nbytes)), "ippm_head_scratch_bytes")
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+class _HeadBf16(torch.autograd.Function):
+    """fc3(relu(fc1(h))) -> logits [B,A] whose forward is ONE kernel and whose backward is four (libippmarl's ippm_head_forward /
+    ippm_head_backward, csrc/head_train.hip) instead of three library GEMMs forward and four backward with bias, threshold and reduction
+    passes between them.  Contract: both operands of every product are rounded to bf16 on their way in, products
+    accumulate in float32, everything else is float32; deterministic, no atomics.  No host synchronisation; the scratch is allocated per
+    call, so the calls record into a hipGraph like the rest of the round."""
+
+    @staticmethod
+    def usable(h: torch.Tensor, fc1: nn.Linear, fc3: nn.Linear) -> bool:
+        tensors = (h, fc1.weight, fc1.bias, fc3.weight, fc3.bias)
+        return (torch.is_grad_enabled() and fc1.bias is not None and fc3.bias is not None and h.is_cuda and h.dim() == 2
+                and h.shape[0] >= 1 and h.shape[1] == 256 and tuple(fc1.weight.shape) == (256, 256) and fc3.weight.dim() == 2
+                and fc3.weight.shape[1] == 256 and 1 <= fc3.weight.shape[0] <= 32
+                and all(t.dtype == torch.float32 and t.device == h.device and not t.is_sparse and t.is_contiguous() for t in tensors)
+                and all(t.requires_grad for t in tensors[1:]))
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w3, b3):
+        from . import _ffi
+        lib = _ffi.load_library()
+        hs, w1, b1, w3, b3 = (t.detach().contiguous() for t in (h, w1, b1, w3, b3))
+        B, A = hs.shape[0], w3.shape[0]
+        a1 = torch.empty((B, 256), dtype=h.dtype, device=h.device)
+        logits = torch.empty((B, A), dtype=h.dtype, device=h.device)
+        _ffi.check(lib.ippm_head_forward(hs.data_ptr(), w1.data_ptr(), b1.data_ptr(), w3.data_ptr(), b3.data_ptr(), B, A, None, a1.data_ptr(),
+                                         logits.data_ptr(), torch.cuda.current_stream(h.device).cuda_stream), "ippm_head_forward")
+        ctx.save_for_backward(hs, w1, w3, a1)
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        from . import _ffi
+        hs, w1, w3, a1 = ctx.saved_tensors
+        lib = _ffi.load_library()
+        B, A = hs.shape[0], w3.shape[0]
+        g = grad_logits.contiguous()
+        gh, gw1, gw3 = torch.empty_like(hs), torch.empty_like(w1), torch.empty_like(w3)
+        gb1 = torch.empty(256, dtype=hs.dtype, device=hs.device)
+        gb3 = torch.empty(A, dtype=hs.dtype, device=hs.device)
+        scratch = _head_scratch(lib, B, A, hs.device)
+        _ffi.check(lib.ippm_head_backward(g.data_ptr(), None, a1.data_ptr(), hs.data_ptr(), w1.data_ptr(), w3.data_ptr(), B, A, scratch.data_ptr(),
+                                          gh.data_ptr(), gw1.data_ptr(), gb1.data_ptr(), gw3.data_ptr(), gb3.data_ptr(),
+                                          torch.cuda.current_stream(hs.device).cuda_stream), "ippm_head_backward")
+        return (gh if ctx.needs_input_grad[0] else None), gw1, gb1, gw3, gb3
+
+
+class _CriticLossBf16(torch.autograd.Function):
+    """(q [B,A], action [B], td [B]) -> (loss = mean (q[b,a_b] - td_b)^2, q_chosen [B]) through ippm_critic_loss, which also writes the
+    gradient of the loss with respect to q; the backward scales it, on the device, by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, q, action, td):
+        from . import _ffi
+        lib = _ffi.load_library()
+        qs, a32, t32 = q.detach().contiguous(), action.to(torch.int32).contiguous(), td.detach().float().contiguous().view(-1)
+        B, A = qs.shape
+        loss = torch.empty((), dtype=q.dtype, device=q.device)
+        q_chosen = torch.empty(B, dtype=q.dtype, device=q.device)
+        dq = torch.empty_like(qs)
+        scratch = _head_scratch(lib, B, A, q.device, losses_only=True)
+        _ffi.check(lib.ippm_critic_loss(qs.data_ptr(), a32.data_ptr(), t32.data_ptr(), B, A, scratch.data_ptr(), loss.data_ptr(),
+                                        q_chosen.data_ptr(), dq.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream), "ippm_critic_loss")
+        ctx.save_for_backward(dq)
+        ctx.mark_non_differentiable(q_chosen)
+        return loss, q_chosen
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_q_chosen):
+        (dq,) = ctx.saved_tensors
+        return dq * grad_loss, None, None
+
+
+class _ActorLossBf16(torch.autograd.Function):
+    """(logits [B,A], q_values, mask, action, eps) -> (loss, adv [B]) of actor/learner.py:52-97 through ippm_actor_loss: softmax, the
+    epsilon mix, K7's advantage, the mask-weighted mean, and the gradient of the loss with respect to the logits in one kernel; the
+    backward scales that gradient, on the device, by the incoming one.  ``eps``: a float, or a device scalar (recorded rounds)."""
+
+    @staticmethod
+    def forward(ctx, logits, q_values, mask, action, eps):
+        from . import _ffi
+        lib = _ffi.load_library()
+        ls, q32 = logits.detach().contiguous(), q_values.detach().float().contiguous()
+        m8, a32 = mask.to(torch.uint8).contiguous(), action.to(torch.int32).contiguous()
+        B, A = ls.shape
+        loss = torch.empty((), dtype=ls.dtype, device=ls.device)
+        adv = torch.empty(B, dtype=ls.dtype, device=ls.device)
+        dlogits = torch.empty_like(ls)
+        eps_dev = eps if isinstance(eps, torch.Tensor) else None
+        scratch = _head_scratch(lib, B, A, ls.device, losses_only=True)
+        _ffi.check(lib.ippm_actor_loss(ls.data_ptr(), q32.data_ptr(), m8.data_ptr(), a32.data_ptr(), B, A, 0.0 if eps_dev is not None else float(eps),
+                                       None if eps_dev is None else eps_dev.data_ptr(), scratch.data_ptr(), loss.data_ptr(), adv.data_ptr(), None,
+                                       dlogits.data_ptr(), torch.cuda.current_stream(ls.device).cuda_stream), "ippm_actor_loss")
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(adv)
+        return loss, adv
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_adv):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * grad_loss, None, None, None, None
+
+
 class _BiasReLU(torch.autograd.Function):
     """relu(x + bias) for a channels-last activation tensor as ONE pass in each direction (libippmarl's ippm_bias_relu_nhwc
     / ippm_bias_relu_backward_nhwc) instead of the bias pass + ReLU pass (and threshold pass + column reduction) PyTorch runs
@@ -403,6 +545,8 @@ class _ConvTrunk(nn.Module):
             h = self.activation(torch.nn.functional.linear(h.permute(0, 2, 3, 1).reshape(h.shape[0], -1), w3, self.conv3.bias))
         else:
             h = self.flatten(self.activation(self.conv3(h)))
+        if _HEAD_UPDATE.get() == "bf16" and _HeadBf16.usable(h, self.fc1, self.fc3):
+            return _HeadBf16.apply(h, self.fc1.weight, self.fc1.bias, self.fc3.weight, self.fc3.bias), h
         return self.fc3(self.activation(self.fc1(h))), h
 
 

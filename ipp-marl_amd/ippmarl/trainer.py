@@ -16,7 +16,7 @@ from . import _ffi
 from . import critic_native
 from .actor_native import NativeActor, resolve_mode
 from .learners import ActorLearner, CriticLearner
-from .networks import ActorNetwork, CriticNetwork, epsilon_schedule, resolve_conv2_update, resolve_trunk_update
+from .networks import ActorNetwork, CriticNetwork, epsilon_schedule, resolve_conv2_update, resolve_head_update, resolve_trunk_update
 from .parallel import GradAllReducer, broadcast_module, episode_ids
 from .vec_env import VecEnv, POLICY_ARGMAX, POLICY_SAMPLE
 
@@ -25,9 +25,13 @@ class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
                  terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None,
-                 actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, conv2_update: Optional[str] = None,
-                 trunk_update: Optional[str] = None):
+                 actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, head_update: Optional[str] = None,
+                 conv2_update: Optional[str] = None, trunk_update: Optional[str] = None):
         self.params = params
+        # head_update: "float32" (the default) or "bf16": fc1, ReLU, fc3, the loss and their gradients of both learners' forward-with-
+        # gradient pass through libippmarl's head kernels (networks._HeadBf16, _CriticLossBf16, _ActorLossBf16); None reads
+        # IPPMARL_HEAD_UPDATE.  Independent of the other switches; every no-grad forward and the diagnostics' minibatches are float32.
+        self.head_update = resolve_head_update(head_update)
         # trunk_update: "float32" (the default) or "bf16": conv1 (networks._Conv5x5Bf16), conv2 and conv3 (networks._Conv3Bf16) of both
         # learners' forward-with-gradient pass and their gradients on the bf16 matrix cores, whatever conv2_update says; None reads
         # IPPMARL_TRUNK_UPDATE.  fc1, fc3, Adam, every no-grad forward and the diagnostics' extra forwards are float32 either way.
@@ -78,9 +82,9 @@ class COMATrainer:
         self.graphs = bool(graphs)
         self._step_graphs = self._update_graph = None
         self.actor_learner = ActorLearner(params, self.actor, self.device, ctx=self.env.ctx, capturable=self.graphs,
-                                          conv2_update=self.conv2_update, trunk_update=self.trunk_update)
-        self.critic_learner = CriticLearner(params, self.critic, self.device, capturable=self.graphs, conv2_update=self.conv2_update,
-                                            trunk_update=self.trunk_update)
+                                          head_update=self.head_update, conv2_update=self.conv2_update, trunk_update=self.trunk_update)
+        self.critic_learner = CriticLearner(params, self.critic, self.device, capturable=self.graphs, head_update=self.head_update,
+                                            conv2_update=self.conv2_update, trunk_update=self.trunk_update)
         for m in (self.actor, self.critic, self.critic_learner.target_critic, self.frozen_target):
             broadcast_module(m)
         # gradients of both nets live in one flat buffer (critic, then actor): the data-parallel average is one all-reduce of a
