@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256) k_conv5x5_pack(const float* __restrict__ 
 
 // ---- forward --------------------------------------------------------------------------------------------------------------------------
 // y[m][n] = sum_k x[patch(m)][k] * W[n][k], m = (sample, oy, ox) of M rows; bias non-null: y = relu(y + bias[n]) with the arithmetic of
-// k_bias_relu (learn.hip), NaN let through.
+// k_bias_relu (learn.hip), NaN let through (ippm_relu).
 template <int PLANES>
 __global__ void __launch_bounds__(256)
 k_conv5x5(const float* __restrict__ in, const uint16_t* __restrict__ w, const float* __restrict__ bias, float* __restrict__ out, int64_t M) {
@@ -134,7 +134,6 @@ k_conv5x5(const float* __restrict__ in, const uint16_t* __restrict__ w, const fl
   }
 
   // D[n][m]: lane holds m = lane & 15 and n = (lane >> 4) * 4 + reg
-  auto relu = [](float v) { return v > 0.f ? v : (v != v ? v : 0.f); };
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) {
     const int64_t m = m0 + wm + mt * 16 + fr;
@@ -145,7 +144,7 @@ k_conv5x5(const float* __restrict__ in, const uint16_t* __restrict__ w, const fl
       float4 v = float4{acc[nt][mt][0], acc[nt][mt][1], acc[nt][mt][2], acc[nt][mt][3]};
       if (bias) {
         const float4 bv = *reinterpret_cast<const float4*>(bias + n);
-        v.x = relu(v.x + bv.x); v.y = relu(v.y + bv.y); v.z = relu(v.z + bv.z); v.w = relu(v.w + bv.w);
+        v.x = ippm_relu(v.x + bv.x); v.y = ippm_relu(v.y + bv.y); v.z = ippm_relu(v.z + bv.z); v.w = ippm_relu(v.w + bv.w);
       }
       *reinterpret_cast<float4*>(out + m * C5_OUT + n) = v;
     }

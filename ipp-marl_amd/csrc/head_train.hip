@@ -4,7 +4,7 @@
 // Numerical contract (as csrc/conv4x4_train.hip): both operands of the six products (z1 = h W1^T, logits = a1 W3^T,
 // ga1 = dlogits W3, gh = gz1 W1, gW1 = gz1^T h, gW3 = dlogits^T a1) are rounded to bf16 (nearest even) on their way into LDS or into a
 // fragment, products accumulate in float32 on mfma_f32_16x16x32_bf16, outputs are float32 and are not rounded again.  Everything else --
-// bias adds, the NaN-passing ReLU of k_bias_relu, gz1 = ga1 [a1 > 0], the bias gradients, the losses' per-row arithmetic -- is float32 on
+// bias adds, the NaN-passing ReLU of k_bias_relu (ippm_relu), gz1 = ga1 [a1 > 0], the bias gradients, the losses' per-row arithmetic -- is float32 on
 // unrounded values (the one sum over the batch that makes a loss is carried in double and rounded once).
 // No float atomics; every output element has one owner and a fixed summation order.  Sums over the batch (gW1, gb1, gW3, gb3, the loss)
 // are per-chunk partial sums (IPPM_HEAD_WGRAD_CHUNK samples) in the scratch, added in chunk order by a second kernel.
@@ -40,7 +40,6 @@ __device__ __forceinline__ uint32_t hd_bf16x2(float lo, float hi) {   // two flo
 __device__ __forceinline__ u32x4 hd_bf16x8(const float (&v)[8]) {
   return u32x4{hd_bf16x2(v[0], v[1]), hd_bf16x2(v[2], v[3]), hd_bf16x2(v[4], v[5]), hd_bf16x2(v[6], v[7])};
 }
-__device__ __forceinline__ float hd_relu(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }   // k_bias_relu's: NaN let through
 
 int64_t hd_chunks(int64_t batch) { return (batch + HC - 1) / HC; }
 
@@ -154,7 +153,7 @@ k_head_rows(const float* __restrict__ x, const float* __restrict__ w1, const flo
       float4 v = float4{acc[nt][mt][0], acc[nt][mt][1], acc[nt][mt][2], acc[nt][mt][3]};
       if (FORWARD) {
         const float4 bv = *reinterpret_cast<const float4*>(b1 + n);
-        v.x = hd_relu(v.x + bv.x); v.y = hd_relu(v.y + bv.y); v.z = hd_relu(v.z + bv.z); v.w = hd_relu(v.w + bv.w);
+        v.x = ippm_relu(v.x + bv.x); v.y = ippm_relu(v.y + bv.y); v.z = ippm_relu(v.z + bv.z); v.w = ippm_relu(v.w + bv.w);
         *reinterpret_cast<uint2*>(&A1s[ml * A1_LD + n]) = make_uint2(hd_bf16x2(v.x, v.y), hd_bf16x2(v.z, v.w));
       }
       if (m < B) *reinterpret_cast<float4*>(out + m * HD + n) = v;
@@ -237,7 +236,9 @@ k_head_gz1(const float* __restrict__ dlogits, const float* __restrict__ scale_de
       const int n = wn + nt * 16 + (lane >> 4) * 4;
       const floatx4 g = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt], af[mt], floatx4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
       const float4 a = *reinterpret_cast<const float4*>(a1 + (m < B ? m : 0) * HD + n);
-      const float4 o = float4{a.x > 0.f ? g[0] : 0.f, a.y > 0.f ? g[1] : 0.f, a.z > 0.f ? g[2] : 0.f, a.w > 0.f ? g[3] : 0.f};
+      // the mask is a FACTOR, as the definition has it (gz1 = ga1 [a1 > 0]): a non-finite ga1 behind a closed ReLU gives NaN, not 0
+      const float4 o = float4{g[0] * (a.x > 0.f ? 1.f : 0.f), g[1] * (a.y > 0.f ? 1.f : 0.f), g[2] * (a.z > 0.f ? 1.f : 0.f),
+                              g[3] * (a.w > 0.f ? 1.f : 0.f)};
       if (m < B) *reinterpret_cast<float4*>(gz1 + m * HD + n) = o;
     }
   }

@@ -2,7 +2,8 @@
 // (11 -> 7 -> 4 -> 1), fc1, and fc3's product.  The two networks differ in the planes of their input (7 / 12: a compile-time parameter
 // of the first layer and of the pack) and in what their head does with fc3's output.  Numerical contract: the
 // input and the weights of every layer are bf16 (round to nearest even), products accumulate in float32 on the matrix cores, the
-// float32 bias is added to the accumulator, ReLU, and the activation is rounded to bf16 once, at the store; fc3's output is float32.
+// float32 bias is added to the accumulator, ReLU (NaN passes: ippm_relu), and the activation is rounded to bf16 once, at the store; fc3's
+// output is float32.
 //
 // Every layer up to fc1 is ONE implicit-GEMM kernel, k_actor_layer: out[m][n] = relu(bias[n] + sum_k A[m][k] W[n][k]) with N = 256,
 // m = (sample, out_y, out_x), k = (tap_y, tap_x, channel) -- tap-major, channel-minor, so the K of a row is read straight from the
@@ -53,6 +54,17 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint16_t ai_bf16(float x) {   // round to nearest even (NaN kept quiet)
   uint32_t u = __float_as_uint(x);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+
+// ai_bf16(ippm_relu(x)) in one pass over the bits: NaN is kept by the test the conversion makes anyway, and what is left of the ReLU --
+// everything with the sign bit set, -0 and -Inf included, becomes +0 -- is one integer max where ippm_relu's two compares and two selects
+// in front of the conversion cost the layer kernel 1.3 % (profiles/r14/)
+__device__ __forceinline__ uint16_t ai_relu_bf16(float x) {
+  uint32_t u = __float_as_uint(x);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+  u = (uint32_t)max((int32_t)u, 0);
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
 }
@@ -214,11 +226,9 @@ k_actor_layer(const void* __restrict__ in_, const uint16_t* __restrict__ w, cons
     for (int nt = 0; nt < 4; ++nt) {
       const int n = n0 + wn + nt * 16 + (lane >> 4) * 4;
       const float4 bv = *reinterpret_cast<const float4*>(bias + n);
-      const float v0 = fmaxf(acc[nt][mt][0] + bv.x, 0.f), v1 = fmaxf(acc[nt][mt][1] + bv.y, 0.f);
-      const float v2 = fmaxf(acc[nt][mt][2] + bv.z, 0.f), v3 = fmaxf(acc[nt][mt][3] + bv.w, 0.f);
-      uint2 o;
-      o.x = (uint32_t)ai_bf16(v0) | ((uint32_t)ai_bf16(v1) << 16);
-      o.y = (uint32_t)ai_bf16(v2) | ((uint32_t)ai_bf16(v3) << 16);
+      uint2 o;   // the NaN-passing ReLU of every bf16 store (ippm_relu), then the rounding
+      o.x = (uint32_t)ai_relu_bf16(acc[nt][mt][0] + bv.x) | ((uint32_t)ai_relu_bf16(acc[nt][mt][1] + bv.y) << 16);
+      o.y = (uint32_t)ai_relu_bf16(acc[nt][mt][2] + bv.z) | ((uint32_t)ai_relu_bf16(acc[nt][mt][3] + bv.w) << 16);
       *reinterpret_cast<uint2*>(out + m * AI_N + n) = o;
     }
   }

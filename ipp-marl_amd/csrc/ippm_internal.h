@@ -179,6 +179,11 @@ __host__ __device__ __forceinline__ size_t ippm_tile_bytes(int S, int vec) { ret
 
 __device__ __forceinline__ float ippm_clipf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
+// ReLU that lets NaN through, as k_bias_relu (learn.hip) and torch.relu do: fmaxf(NaN, 0) = 0 would hide a diverged activation.  The one
+// ReLU of every bf16 matrix-core store (conv5x5_train.hip, head_train.hip, and -- folded into the rounding that follows it there, as
+// ai_relu_bf16 -- ippm_bf16_net.h).
+__device__ __forceinline__ float ippm_relu(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
+
 // Maps are stored as float32 LOG-ODDS L = ln(p/(1-p)) (DESIGN.md "log-odds storage"): the reference's
 // clip(p, 1e-4, 0.9999) is clamp(L, -lc, +lc) with lc = ln(0.9999/0.0001), its Bayes update is an add.
 // (v_med3_f32: one instruction; fminf(fmaxf()) costs five, three of them NaN canonicalisations)
