@@ -556,6 +556,44 @@ int ippm_head_backward(const float* dlogits, const float* scale_dev, const float
                        const float* fc3_w, int64_t batch, int32_t n_actions, void* scratch, float* gh, float* g_fc1_w, float* g_fc1_b,
                        float* g_fc3_w, float* g_fc3_b, void* stream);
 
+/* ---- native Adam (csrc/optim.hip): the optimizer step of the learners (actor/learner.py:32, critic/learner.py:48: torch.optim.Adam(parameters,
+ * lr) with its defaults -- betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad) for up to 16 float32 tensors in ONE kernel launch, which
+ * can also clear the gradients and rewrite a network's bf16 inference pack from the stepped parameters.  No context needed.
+ * Arithmetic contract (a contract of this library, not a promise to match any other implementation's bits).  Per step,
+ * scalars in double:  b1p <- b1p * beta1;  b2p <- b2p * beta2 (one multiplication each, no pow);  step = float(lr / (1 - b1p));
+ * rs = float(sqrt(1 - b2p));  w1 = float(1 - beta1);  w2 = float(1 - beta2);  B2 = float(beta2);  E = float(eps).  Per element, float32, every
+ * operation rounded on its own in this order, nothing contracted into an FMA:
+ *     m <- m + w1 (g - m);   v <- B2 v + w2 (g g);   den = sqrtf(v) / rs + E;   p <- p - step (m / den).
+ * NaN and Inf propagate as IEEE arithmetic propagates them: a non-finite gradient element reaches its own p, m, v (and pack element) only.
+ * Float32 subnormal operands are outside the contract.  Deterministic: every element has one owner, there are no float atomics.
+ * The state blob is caller-owned, 16-byte aligned, ippm_adam_state_bytes long, and laid out as follows (a binding may hand out views):
+ *     byte 0   int64  t        steps taken            byte 8   double b1p = beta1^t       byte 16  double b2p = beta2^t
+ *     byte 24  uint32 ticket   0 between launches     bytes 28-63 padding
+ *     byte 64  for tensor 0, 1, ... in turn: float m[numel], padded to a multiple of 4 floats, then float v[numel], padded likewise
+ *              (so every span starts 16-byte aligned: tensor i's m is (numel_0' + ... + numel_{i-1}') * 8 bytes behind byte 64, numel' = numel
+ *              rounded up to a multiple of 4, and its v follows numel_i' * 4 bytes later).
+ *   ippm_adam_state_bytes  size of the blob for n_tensors in [1, 16] tensors of numel[i] in [1, 2^36] elements.
+ *   ippm_adam_init         one kernel: t = 0, both powers 1, ticket 0, every moment (and the padding) 0, whatever the blob held.
+ *   ippm_adam_step         one kernel, capturable: nothing the host passes changes from step to step -- the counters live in the blob and
+ *                          advance inside the launch (the last workgroup to finish writes them; no workgroup waits on another), so a
+ *                          recorded launch steps again at every replay.  params / grads: HOST arrays of n_tensors device pointers (they
+ *                          travel as kernel arguments).  flags & IPPM_ADAM_ZERO_GRAD: the lane that read a gradient element stores +0.0f
+ *                          there.  packed != NULL (16-byte aligned; pack_planes = 7 or 12, else both 0 / NULL): the tensors must be the ten
+ *                          of a network in the order conv1.w, conv1.b, conv2.w, conv2.b, conv3.w, conv3.b, fc1.w, fc1.b, fc3.w, fc3.b with
+ *                          the sizes of that network for n_actions in [1, 32], and the same launch rewrites EVERY byte of the pack:
+ *                          afterwards it equals what ippm_actor_pack (7) / ippm_critic_pack (12) writes from the stepped parameters,
+ *                          whatever it held before.
+ * -1 with ippm_last_error set for a null pointer, n_tensors outside [1, 16], a numel outside [1, 2^36], a state or pack that is not 16-byte
+ * aligned, lr or eps that is not finite or negative, a beta outside [0, 1), unknown flags, pack_planes other than 0, 7, 12, a pack without
+ * pack_planes (or the reverse), a pack with n_tensors != 10, n_actions outside [1, 32] or sizes that are not that network's; nothing is
+ * launched then.  No host synchronisation, no allocation, launches on `stream` only. */
+#define IPPM_ADAM_ZERO_GRAD 1
+#define IPPM_ADAM_MAX_TENSORS 16
+int ippm_adam_state_bytes(const int64_t* numel, int32_t n_tensors, int64_t* bytes);
+int ippm_adam_init(void* state, const int64_t* numel, int32_t n_tensors, void* stream);
+int ippm_adam_step(void* state, float* const* params, float* const* grads, const int64_t* numel, int32_t n_tensors, double lr, double beta1,
+                   double beta2, double eps, int32_t flags, int32_t pack_planes, int32_t n_actions, void* packed, void* stream);
+
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
  * Q(s_t)[a_t] -> td_target, discounted_return float. */

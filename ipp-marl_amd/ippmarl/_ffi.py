@@ -125,6 +125,9 @@ PROTOTYPES = {
     "ippm_critic_loss": [P, P, P, I64, I32, P, P, P, P, P],
     "ippm_actor_loss": [P, P, P, P, I64, I32, C.c_float, P, P, P, P, P, P, P],
     "ippm_head_backward": [P, P, P, P, P, P, I64, I32, P, P, P, P, P, P, P],
+    "ippm_adam_state_bytes": [P, I32, P],
+    "ippm_adam_init": [P, P, I32, P],
+    "ippm_adam_step": [P, P, P, P, I32, C.c_double, C.c_double, C.c_double, C.c_double, I32, I32, I32, P, P],
     "ippm_ig_candidates": [P, P, P, P, P, I32, P],
     "ippm_ig_select": [P, P, P, P, I32, P, P, I32, P],
     "ippm_f1_counts": [P, P, P, I32, C.c_float, P, I32, P],

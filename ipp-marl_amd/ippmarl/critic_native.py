@@ -43,6 +43,11 @@ class NativeCritic(NativeNet):
         self.refresh()
         return self._forward(states, None, True)[0]
 
+    def after_native_step(self, states: torch.Tensor) -> torch.Tensor:
+        """``after_step`` behind a native Adam step that had this pack attached (optim_native.NativeAdam.attach_pack): the step's launch
+        has rewritten the pack already, so Q [B,A] of ``states`` is the only launch."""
+        return self._forward(states, None, True)[0]
+
     def _forward(self, states, actions, want_q):
         states = self._input(states)
         B = states.shape[0]

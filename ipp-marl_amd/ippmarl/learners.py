@@ -1,6 +1,6 @@
 """COMA learners on tensors: critic TD regression (critic/learner.py:58-198) and actor policy gradient with the
 counterfactual baseline (actor/learner.py:36-168).  The baseline/advantage arithmetic runs in the HIP kernel K7
-(ippm_coma_advantage); autograd, Adam and the convnets are PyTorch.  Metric-only work of the reference (KL via an
+(ippm_coma_advantage); autograd, Adam and the convnets are PyTorch (opt-in native pieces: the ``*_update`` switches and ``adam``).  Metric-only work of the reference (KL via an
 extra forward pass, gradient-norm dumps, explained variance) is computed by ippmarl.metrics from the per-minibatch
 records the learners keep in ``.last`` when ``collect`` is switched on."""
 from __future__ import annotations
@@ -11,6 +11,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _ffi
+from . import optim_native
 from .networks import conv2_update as conv2_update_mode, resolve_conv2_update
 from .networks import resolve_trunk_update, trunk_update as trunk_update_mode
 from .networks import _ActorLossBf16, _CriticLossBf16, head_update as head_update_mode, resolve_head_update
@@ -25,10 +26,22 @@ def _adam(parameters, lr: float, capturable: bool):
     return torch.optim.Adam(parameters, lr=lr)
 
 
+def _optimizer(module, lr: float, capturable: bool, adam: str):
+    """adam="torch": ``_adam`` over the module's parameters, exactly as before the switch existed.  "native": optim_native.NativeAdam
+    over the same list, stepping the ten tensors the network uses (``fc2`` never has a gradient, and torch.optim.Adam never touches it
+    either) -- the same kernel whether the round is recorded or not."""
+    if adam == "native":
+        return optim_native.NativeAdam(module.parameters(), lr, managed=optim_native.used_parameters(module))
+    return _adam(module.parameters(), lr, capturable)
+
+
 class CriticLearner:
-    def __init__(self, params: Dict, critic, device, capturable: bool = False, head_update: str = "float32", conv2_update: str = "float32",
-                 trunk_update: str = "float32"):
+    def __init__(self, params: Dict, critic, device, capturable: bool = False, adam: str = "torch", head_update: str = "float32",
+                 conv2_update: str = "float32", trunk_update: str = "float32"):
         self.params = params
+        # the optimizer: "torch" (torch.optim.Adam), or "native" (optim_native.NativeAdam: one launch steps the net, clears its gradients
+        # and, where an inference pack is kept, rewrites it)
+        self.adam = optim_native.resolve_mode(adam)
         # fc1, ReLU, fc3 and the loss of the same pass: "float32", or "bf16" (networks._HeadBf16, _CriticLossBf16); independent of the others
         self.head_update = resolve_head_update(head_update)
         # conv1, conv2 and conv3 of the same pass: "float32", or "bf16" (networks.trunk_update; implies the bf16 conv2)
@@ -45,7 +58,7 @@ class CriticLearner:
         self.target_update_mode = net["critic"]["target_update_mode"]
         self.tau = net["critic"]["tau"]
         # capturable: the step count lives on the device, so that optimizer steps can be recorded into a hipGraph (trainer.capture_graphs)
-        self.optimizer = _adam(self.critic.parameters(), self.lr, capturable)
+        self.optimizer = _optimizer(self.critic, self.lr, capturable, self.adam)
         self.optimizer.zero_grad()
         self.collect = False   # keep the tensors ippmarl.metrics.critic_metrics needs in self.last
         self.last = None
@@ -86,9 +99,15 @@ class CriticLearner:
         """Second half: Adam step, then the POST-step Q handed to the actor (critic/learner.py:93-105).  -> q_new [B,A]"""
         states, actions, td_targets, loss, q_chosen = self._pending
         self._pending = None
-        self.optimizer.step()
-        if self.inference is not None and not self.collect:
-            return self.inference.after_step(states)
+        if self.adam == "native" and self.inference is not None:
+            self.optimizer.attach_pack(self.inference)       # the step's launch rewrites the pack: nothing to repack afterwards
+            self.optimizer.step()
+            if not self.collect:
+                return self.inference.after_native_step(states)
+        else:
+            self.optimizer.step()
+            if self.inference is not None and not self.collect:
+                return self.inference.after_step(states)
         # (diagnostics keep the module's forward: the metrics need logp)
         with torch.no_grad():
             q_new, logp = self.critic(states)
@@ -107,9 +126,10 @@ class CriticLearner:
 
 
 class ActorLearner:
-    def __init__(self, params: Dict, actor, device, ctx: Optional[_ffi.Context] = None, capturable: bool = False,
+    def __init__(self, params: Dict, actor, device, ctx: Optional[_ffi.Context] = None, capturable: bool = False, adam: str = "torch",
                  head_update: str = "float32", conv2_update: str = "float32", trunk_update: str = "float32"):
         self.params = params
+        self.adam = optim_native.resolve_mode(adam)             # as CriticLearner's
         self.head_update = resolve_head_update(head_update)     # as CriticLearner's (networks._HeadBf16, _ActorLossBf16)
         self.conv2_update = resolve_conv2_update(conv2_update)   # as CriticLearner's
         self.trunk_update = resolve_trunk_update(trunk_update)
@@ -118,7 +138,7 @@ class ActorLearner:
         self.ctx = ctx
         self.n_actions = params["experiment"]["constraints"]["num_actions"]
         self.lr = params["networks"]["actor"]["learning_rate"]
-        self.optimizer = _adam(self.actor.parameters(), self.lr, capturable)
+        self.optimizer = _optimizer(self.actor, self.lr, capturable, self.adam)
         self.optimizer.zero_grad()
         self.collect = False
         self.last = None

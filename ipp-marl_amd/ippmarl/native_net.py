@@ -21,10 +21,11 @@ _LAYERS = ("conv1", "conv2", "conv3", "fc1", "fc3")   # fc2 is never used by the
 
 
 def resolve(value: Optional[str], env_var: str, what: str) -> str:
-    """An inference switch: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises."""
+    """A "torch" / "native" switch (the inference paths; "adam": the learners' optimizer): the argument, else the environment variable,
+    else "torch"; anything but "torch" / "native" raises."""
     mode = value if value is not None else os.environ.get(env_var, "") or "torch"
     if mode not in MODES:
-        raise ValueError(f"{what} inference must be one of {MODES}, got {mode!r}")
+        raise ValueError(f"{what if what == 'adam' else what + ' inference'} must be one of {MODES}, got {mode!r}")
     return mode
 
 

@@ -14,6 +14,7 @@ import torch
 
 from . import _ffi
 from . import critic_native
+from . import optim_native
 from .actor_native import NativeActor, resolve_mode
 from .learners import ActorLearner, CriticLearner
 from .networks import ActorNetwork, CriticNetwork, epsilon_schedule, resolve_conv2_update, resolve_head_update, resolve_trunk_update
@@ -25,9 +26,13 @@ class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
                  terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None,
-                 actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, head_update: Optional[str] = None,
-                 conv2_update: Optional[str] = None, trunk_update: Optional[str] = None):
+                 actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, adam: Optional[str] = None,
+                 head_update: Optional[str] = None, conv2_update: Optional[str] = None, trunk_update: Optional[str] = None):
         self.params = params
+        # adam: "torch" (torch.optim.Adam, the default) or "native" (optim_native.NativeAdam: one launch of libippmarl steps a net, clears
+        # its gradients and rewrites the inference pack where one is kept -- the same kernel whether ``graphs`` is set or not); None reads
+        # IPPMARL_ADAM.  Independent of the other switches.
+        self.adam = optim_native.resolve_mode(adam)
         # head_update: "float32" (the default) or "bf16": fc1, ReLU, fc3, the loss and their gradients of both learners' forward-with-
         # gradient pass through libippmarl's head kernels (networks._HeadBf16, _CriticLossBf16, _ActorLossBf16); None reads
         # IPPMARL_HEAD_UPDATE.  Independent of the other switches; every no-grad forward and the diagnostics' minibatches are float32.
@@ -78,13 +83,14 @@ class COMATrainer:
         # few microseconds of work each, Python between them); capture_graphs() records every rollout step and the whole update
         # into hipGraphs.  graphs=True changes the optimizer IMPLEMENTATION for every round of this trainer, recorded or not: both
         # Adam instances are torch's fused capturable form (step counters on the device, one kernel per step), whose update agrees
-        # with the default form to float32 rounding, not bit for bit; their state is not part of save_actor's pickle.
+        # with the default form to float32 rounding, not bit for bit; their state is not part of save_actor's pickle.  (adam="native"
+        # has one implementation for both.)
         self.graphs = bool(graphs)
         self._step_graphs = self._update_graph = None
-        self.actor_learner = ActorLearner(params, self.actor, self.device, ctx=self.env.ctx, capturable=self.graphs,
+        self.actor_learner = ActorLearner(params, self.actor, self.device, ctx=self.env.ctx, capturable=self.graphs, adam=self.adam,
                                           head_update=self.head_update, conv2_update=self.conv2_update, trunk_update=self.trunk_update)
-        self.critic_learner = CriticLearner(params, self.critic, self.device, capturable=self.graphs, head_update=self.head_update,
-                                            conv2_update=self.conv2_update, trunk_update=self.trunk_update)
+        self.critic_learner = CriticLearner(params, self.critic, self.device, capturable=self.graphs, adam=self.adam,
+                                            head_update=self.head_update, conv2_update=self.conv2_update, trunk_update=self.trunk_update)
         for m in (self.actor, self.critic, self.critic_learner.target_critic, self.frozen_target):
             broadcast_module(m)
         # gradients of both nets live in one flat buffer (critic, then actor): the data-parallel average is one all-reduce of a
@@ -190,6 +196,8 @@ class COMATrainer:
         if self._native is None or self._native.module is not self.actor:
             self._native = NativeActor(self.actor, self.device)
             self._native.reserve(self.E * self.N)
+            if self.adam == "native" and self.actor is self.actor_learner.actor:
+                self.actor_learner.optimizer.attach_pack(self._native)     # every actor step rewrites this pack in its own launch
         return self._native
 
     def target_module(self):
@@ -210,7 +218,11 @@ class COMATrainer:
         """Repack the native actor from the module's current parameters (no-op on the torch path): update() does it after its
         optimizer steps; call it after loading a state dict into ``self.actor`` by other means."""
         if self.actor_inference == "native":
-            self.native_actor().refresh()
+            native = self.native_actor()
+            if self.adam == "native" and self.actor_learner.optimizer._pack is native:
+                native.sync()      # (the optimizer's steps kept the pack and its stamp current: a host-side check, no launch)
+            else:
+                native.refresh()
 
     def last_agent_reward(self) -> torch.Tensor:
         """[E, 2] DeepQ (relative, absolute) reward of the last agent that flies in each env: what the reference's wrapper returns
