@@ -654,7 +654,8 @@ int ippm_terrain_field(ippm_ctx* ctx, const int64_t* episode, const float* amp, 
 int ippm_terrain_pack(ippm_ctx* ctx, const float* field, const uint32_t* range_keys, uint8_t* truth, int32_t n_envs, void* stream);
 /* ippm_terrain_truth = ippm_terrain_field(spec = NULL) + ippm_terrain_pack without ever storing the field: the second transform
  * pass runs twice (once for the field's min / max, once more for the threshold bits, same arithmetic), which moves half the bytes
- * of writing the field and reading it back.  work: complex64 [E,gy/2+1,gx] scratch; range_keys: uint32 [4*E + 4] scratch (per env:
+ * of writing the field and reading it back -- or, for sides of 128 / 256 cells in batches of 128 envs or more, runs once with one
+ * workgroup per env that holds the env's rows in registers; the same truth and keys bit for bit.  work: complex64 [E,gy/2+1,gx] scratch; range_keys: uint32 [4*E + 4] scratch (per env:
  * min key, max key, and two words + a trailing record for the one-launch form of the pass, IPPM_TERRAIN_ONE_LAUNCH=1: arrivals, a
  * fault word that stays 0 unless an in-launch wait gave up, the launch's ticket counter). */
 int ippm_terrain_truth(ippm_ctx* ctx, const int64_t* episode, const float* amp, float* work, uint32_t* range_keys, uint8_t* truth,

@@ -250,6 +250,78 @@ __global__ __launch_bounds__((FourStep<N1, N2, Q>::THREADS)) void k_terrain_fft_
   }
 }
 
+// ---- the bodies every form of pass Y shares (statement for statement one arithmetic: a row's bits do not depend on the form) ----
+// thread (q_in, i2)'s N1 inputs of one row pair: src = the pair's first bin (16-byte aligned: the row and gx are even)
+template <int N1, int N2>
+__device__ __forceinline__ void terrain_y_load(float2 (&v)[N1], const float2* __restrict__ src, int gx, int i2) {
+  constexpr int gy = N1 * N2;
+#pragma unroll
+  for (int i1 = 0; i1 < N1; ++i1) {
+    const int i = i1 * N2 + i2, m = 2 * i > gy ? gy - i : i;   // bins above gy/2 are the conjugate mirror
+    const float4 ab = *reinterpret_cast<const float4*>(src + (size_t)m * gx);
+    float2 a = make_float2(ab.x, ab.y), b = make_float2(ab.z, ab.w);
+    if (2 * i > gy) { a.y = -a.y; b.y = -b.y; }
+    if (i == 0 || 2 * i == gy) { a.y = 0.0f; b.y = 0.0f; }     // self-mirrored bins of a real transform
+    v[i1] = make_float2(a.x - b.y, a.y + b.x);                 // A + iB
+  }
+}
+// (min, max) of a thread's outputs, then of its wavefront
+template <int N2>
+__device__ __forceinline__ void terrain_y_range(const float2 (&o)[N2], float& lo, float& hi) {
+#pragma unroll
+  for (int k2 = 0; k2 < N2; ++k2) {
+    lo = fminf(lo, fminf(o[k2].x, o[k2].y));
+    hi = fmaxf(hi, fmaxf(o[k2].x, o[k2].y));
+  }
+}
+__device__ __forceinline__ void terrain_wave_range(float& lo, float& hi) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, m, 64));
+    hi = fmaxf(hi, __shfl_xor(hi, m, 64));
+  }
+}
+// threshold and pack the rows x0 .. x0 + 2 Q - 1 held by FourStep<N1, N2, Q>::THREADS threads (tid: the thread's number among
+// them; they are whole wavefronts): for one k2 a wavefront holds columns k1 + N1 k2 of 64 / N1 rows, i.e. N1 consecutive bits of
+// each of those rows' bit strings; lane L < 64 / N1 collects row L's chunks into 32-bit words and stores every completed word
+//
+// The truth bit of a cell f is (f - lo) / span >= 0.5f.  QUOTIENT = false decides it WITHOUT the division (a correctly rounded
+// float division is ~11 instructions, 64 of them per thread of the whole-field form: a quarter of that kernel): with d = f - lo,
+// rounded as in the quotient form, and h = span / 2, the bit is d >= h.  Proof, for a normal h (so h is exact): d >= h gives
+// d / span >= 1/2, and rounding is monotone; d < h means d <= pred(h) <= h (1 - 2^-24), so d / span <= 1/2 - 2^-25 = pred(0.5f), a
+// float, and the rounded quotient is below 0.5f.  NaNs give 0 in both forms.  The caller takes this form only for
+// 2^-100 <= span <= 2^100 (TERRAIN_SPAN_DIRECT); zero, tiny, infinite and NaN spans keep the quotient.
+#define TERRAIN_SPAN_DIRECT(span) ((span) >= 0x1p-100f && (span) <= 0x1p100f)
+template <bool QUOTIENT>
+__device__ __forceinline__ bool terrain_bit(float f, float lo, float span, float half) {
+  return QUOTIENT ? (f - lo) / span >= 0.5f : f - lo >= half;
+}
+template <int N1, int N2, int Q, bool QUOTIENT = true>
+__device__ __forceinline__ void terrain_y_pack(const float2 (&o)[N2], bool out_active, float lo, float span, uint32_t* __restrict__ out,
+                                               int x0, int tid) {
+  static_assert(N1 == 8 || N1 == 16 || N1 == 32, "a chunk must not straddle a 32-bit word");
+  constexpr int gy = N1 * N2;
+  const float half = 0.5f * span;
+  const int lane = tid & 63, rows_per_wave = 64 / N1;
+  const int my_q = (tid >> 6) * rows_per_wave + lane;          // the row (slot) this lane stores for, if lane < rows_per_wave
+  const bool storer = lane < rows_per_wave && my_q < Q;
+  const size_t row_a = ((size_t)(x0 + 2 * my_q) * gy) >> 5, row_b = ((size_t)(x0 + 2 * my_q + 1) * gy) >> 5;
+  uint32_t wa = 0, wb = 0;
+#pragma unroll
+  for (int k2 = 0; k2 < N2; ++k2) {
+    const uint64_t ba = __ballot(out_active && terrain_bit<QUOTIENT>(o[k2].x, lo, span, half));
+    const uint64_t bb = __ballot(out_active && terrain_bit<QUOTIENT>(o[k2].y, lo, span, half));
+    const uint32_t mask = N1 == 32 ? 0xFFFFFFFFu : ((1u << (N1 & 31)) - 1u);
+    const int sh = (k2 * N1) & 31;
+    wa |= ((uint32_t)(ba >> ((N1 * lane) & 63)) & mask) << sh;
+    wb |= ((uint32_t)(bb >> ((N1 * lane) & 63)) & mask) << sh;
+    if (((k2 + 1) * N1) % 32 == 0) {   // (compile time) a word is complete
+      if (storer) { out[row_a + ((k2 * N1) >> 5)] = wa; out[row_b + ((k2 * N1) >> 5)] = wb; }
+      wa = 0; wb = 0;
+    }
+  }
+}
+
 // pass Y: sequences are the x rows (length gy = N1 * N2 after the Hermitian extension).  The rows are real, so ONE complex
 // transform yields TWO of them: with A, B the Hermitian-extended spectra of rows xa and xb, the inverse transform of A + iB is
 // a + ib with a, b the two real rows.  A workgroup takes 2 Q rows, slot q the NEIGHBOURS xa = x0 + 2 q, xb = xa + 1 (their
@@ -287,39 +359,23 @@ __global__ __launch_bounds__((FourStep<N1, N2, Q>::THREADS)) void k_terrain_fft_
   const int q_in = tid % Q, i2 = tid / Q, k1 = tid % N1, q_out = tid / N1;
   const bool in_active = i2 < N2, out_active = q_out < Q;
   float2 v[N1], o[N2];
-  if (in_active) {
-    const float2* src = work + (size_t)e * hy * gx + x0 + 2 * q_in;   // (16-byte aligned: x0 and gx are even)
-#pragma unroll
-    for (int i1 = 0; i1 < N1; ++i1) {
-      const int i = i1 * N2 + i2, m = 2 * i > gy ? gy - i : i;   // bins above gy/2 are the conjugate mirror
-      const float4 ab = *reinterpret_cast<const float4*>(src + (size_t)m * gx);
-      float2 a = make_float2(ab.x, ab.y), b = make_float2(ab.z, ab.w);
-      if (2 * i > gy) { a.y = -a.y; b.y = -b.y; }
-      if (i == 0 || 2 * i == gy) { a.y = 0.0f; b.y = 0.0f; }     // self-mirrored bins of a real transform
-      v[i1] = make_float2(a.x - b.y, a.y + b.x);                 // A + iB
-    }
-  }
+  if (in_active) terrain_y_load<N1, N2>(v, work + (size_t)e * hy * gx + x0 + 2 * q_in, gx, i2);
   fs.run(v, o, q_in, i2, in_active, q_out, k1, out_active);
   if (MODE != 2) {
     float lo = INFINITY, hi = -INFINITY;
     if (out_active) {
-      float* dst = field + ((size_t)e * gx + x0 + 2 * q_out) * gy + k1;
+      if (MODE == 0) {
+        float* dst = field + ((size_t)e * gx + x0 + 2 * q_out) * gy + k1;
 #pragma unroll
-      for (int k2 = 0; k2 < N2; ++k2) {
-        if (MODE == 0) {
+        for (int k2 = 0; k2 < N2; ++k2) {
           dst[N1 * k2] = o[k2].x;
           dst[(size_t)gy + N1 * k2] = o[k2].y;
         }
-        lo = fminf(lo, fminf(o[k2].x, o[k2].y));
-        hi = fmaxf(hi, fmaxf(o[k2].x, o[k2].y));
       }
+      terrain_y_range<N2>(o, lo, hi);
     }
     if (range_keys) {   // wavefront, then workgroup reduction; one atomic pair per workgroup
-#pragma unroll
-      for (int m = 32; m > 0; m >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, m, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, m, 64));
-      }
+      terrain_wave_range(lo, hi);
       __shared__ float s_lo[8], s_hi[8];
       constexpr int NW = FourStep<N1, N2, Q>::THREADS / 64;
       if ((tid & 63) == 0) { s_lo[tid >> 6] = lo; s_hi[tid >> 6] = hi; }
@@ -363,32 +419,69 @@ __global__ __launch_bounds__((FourStep<N1, N2, Q>::THREADS)) void k_terrain_fft_
     __syncthreads();     // the env's (min, max) are final
   }
   {
-    // threshold and pack: for one k2 a wavefront holds columns k1 + N1 k2 of 64 / N1 rows, i.e. N1 consecutive bits of each of
-    // those rows' bit strings; lane L < 64 / N1 collects row L's chunks into 32-bit words and stores every completed word
-    static_assert(N1 == 8 || N1 == 16 || N1 == 32, "a chunk must not straddle a 32-bit word");
     // (MODE 3: written by other workgroups of this launch, possibly on other XCDs -- thread 0 fetched them at device scope)
     const uint32_t key_lo = MODE == 3 ? s_keys[0] : range_keys[key_stride * e];
     const uint32_t key_hi = MODE == 3 ? s_keys[1] : range_keys[key_stride * e + 1];
     const float lo = key_value(key_lo), span = key_value(key_hi) - lo;
-    const int lane = tid & 63, rows_per_wave = 64 / N1;
-    const int my_q = (tid >> 6) * rows_per_wave + lane;          // the row (slot) this lane stores for, if lane < rows_per_wave
-    const bool storer = lane < rows_per_wave && my_q < Q;
-    uint32_t* out = truth32 + (size_t)e * truth_words;
-    const size_t row_a = ((size_t)(x0 + 2 * my_q) * gy) >> 5, row_b = ((size_t)(x0 + 2 * my_q + 1) * gy) >> 5;
-    uint32_t wa = 0, wb = 0;
+    terrain_y_pack<N1, N2, Q>(o, out_active, lo, span, truth32 + (size_t)e * truth_words, x0, tid);
+  }
+}
+
+// pass Y, whole-field form (the episode reset's, for fields of 128 or 256 cells a side): ONE workgroup per env, so the field's
+// (min, max) is a workgroup reduction and every row is transformed once.  The workgroup is TERRAIN_FIELD_GROUPS groups of
+// FourStep::THREADS threads, each with a FourStep of its own; group g takes the row blocks ROUND * GROUPS + g (2 Q rows each, as in
+// the form above) and keeps every round's outputs in registers (16 float2 per round; ROUNDS = gx / (2 Q GROUPS) = 1 or 2).  Then:
+// (min, max) by wavefront shuffle and LDS, the two keys stored where the two-pass form leaves them, and the held rows thresholded
+// (without the division where the span allows it, terrain_bit above: the passes are VALU-issue-bound, and with the quotient this
+// form gained 34 us per 1024 fields of 256^2 instead of 45).  Nothing crosses workgroups: no atomics, no counters, no waiting.
+// Budget at <16, 16, 16> (compiler's resource remarks, profiles/r16/README.md): 148 KB of the CU's 160 KiB LDS, i.e. one workgroup =
+// 16 wavefronts per CU, which is what LDS allows the two-pass form too (four workgroups of 256 threads).
+#define TERRAIN_FIELD_GROUPS 4
+template <int N1, int N2, int Q, int ROUNDS>
+__global__ __launch_bounds__((TERRAIN_FIELD_GROUPS * FourStep<N1, N2, Q>::THREADS)) void k_terrain_fft_y_field(
+    const ippm_config* __restrict__ c, const float2* __restrict__ work, uint32_t* __restrict__ range_keys,
+    const float2* __restrict__ roots1024, uint32_t* __restrict__ truth32, int truth_words, int key_stride) {
+  using FS = FourStep<N1, N2, Q>;
+  constexpr int G = TERRAIN_FIELD_GROUPS, NW = G * FS::THREADS / 64, gy = N1 * N2, hy = gy / 2 + 1;
+  static_assert(FS::THREADS % 64 == 0, "a group is whole wavefronts");
+  __shared__ FS fs[G];
+  __shared__ uint32_t s_lo[NW], s_hi[NW];
+  const int e = blockIdx.x, grp = threadIdx.x / FS::THREADS, tid = threadIdx.x % FS::THREADS, gx = c->grid_x;   // gx == 2 Q G ROUNDS
+  FS& f = fs[grp];
+  for (int i = tid; i < N1 * N2; i += FS::THREADS) f.twn[i] = roots1024[i * (1024 / (N1 * N2))];   // (FourStep::init_twiddles, per group)
+  __syncthreads();
+  const int q_in = tid % Q, i2 = tid / Q, k1 = tid % N1, q_out = tid / N1;
+  const bool in_active = i2 < N2, out_active = q_out < Q;
+  float2 o[ROUNDS][N2];
+  float lo = INFINITY, hi = -INFINITY;
 #pragma unroll
-    for (int k2 = 0; k2 < N2; ++k2) {
-      const uint64_t ba = __ballot(out_active && (o[k2].x - lo) / span >= 0.5f);
-      const uint64_t bb = __ballot(out_active && (o[k2].y - lo) / span >= 0.5f);
-      const uint32_t mask = N1 == 32 ? 0xFFFFFFFFu : ((1u << (N1 & 31)) - 1u);
-      const int sh = (k2 * N1) & 31;
-      wa |= ((uint32_t)(ba >> ((N1 * lane) & 63)) & mask) << sh;
-      wb |= ((uint32_t)(bb >> ((N1 * lane) & 63)) & mask) << sh;
-      if (((k2 + 1) * N1) % 32 == 0) {   // (compile time) a word is complete
-        if (storer) { out[row_a + ((k2 * N1) >> 5)] = wa; out[row_b + ((k2 * N1) >> 5)] = wb; }
-        wa = 0; wb = 0;
-      }
-    }
+  for (int r = 0; r < ROUNDS; ++r) {
+    const int x0 = (r * G + grp) * 2 * Q;
+    float2 v[N1];
+    if (in_active) terrain_y_load<N1, N2>(v, work + (size_t)e * hy * gx + x0 + 2 * q_in, gx, i2);
+    if (r > 0) __syncthreads();     // the group has read the previous round out of its xbuf (after the loads: they may be issued before)
+    f.run(v, o[r], q_in, i2, in_active, q_out, k1, out_active);
+    if (out_active) terrain_y_range<N2>(o[r], lo, hi);
+  }
+  terrain_wave_range(lo, hi);
+  if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = order_key(lo); s_hi[threadIdx.x >> 6] = order_key(hi); }
+  __syncthreads();
+  uint32_t key_lo = s_lo[0], key_hi = s_hi[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) { key_lo = min(key_lo, s_lo[w]); key_hi = max(key_hi, s_hi[w]); }
+  if (threadIdx.x == 0) {           // what the two-pass form's atomics leave there
+    range_keys[key_stride * e] = key_lo;
+    range_keys[key_stride * e + 1] = key_hi;
+  }
+  lo = key_value(__builtin_amdgcn_readfirstlane(key_lo));      // (the same in every lane: a scalar branch below)
+  const float span = key_value(__builtin_amdgcn_readfirstlane(key_hi)) - lo;
+  uint32_t* out = truth32 + (size_t)e * truth_words;
+  if (TERRAIN_SPAN_DIRECT(span)) {
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) terrain_y_pack<N1, N2, Q, false>(o[r], out_active, lo, span, out, (r * G + grp) * 2 * Q, tid);
+  } else {
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) terrain_y_pack<N1, N2, Q, true>(o[r], out_active, lo, span, out, (r * G + grp) * 2 * Q, tid);
   }
 }
 
@@ -587,6 +680,33 @@ static int terrain_launch_y(ippm_ctx* ctx, const float2* work2, float* field, ui
   return 0;
 }
 
+// Batches from which ippm_terrain_truth takes the whole-field form: it runs ONE workgroup per env and CU, so a small batch leaves
+// most of the device's 256 CUs empty where the two-pass form spreads an env over gx / 32 workgroups.  Measured (a whole synthesis of
+// 256^2 fields, two-pass against whole-field, profiles/r16/terrain_synthesis_ab.txt): 1024 envs 205 -> 160 us, 512: 114 -> 88,
+// 256: 65 -> 46.5, 128: 41.8 -> 36.6, 64: 30.2 -> 30.6 (level); 128^2 fields likewise (128 envs: 20.6 -> 17.3).
+#ifndef TERRAIN_FIELD_MIN_ENVS
+#define TERRAIN_FIELD_MIN_ENVS 128
+#endif
+static bool terrain_field_form(const ippm_ctx* ctx, int n_envs) {
+  const int gx = ctx->cfg.grid_x, gy = ctx->cfg.grid_y;
+  return (gx == 128 || gx == 256) && (gy == 128 || gy == 256) && n_envs >= TERRAIN_FIELD_MIN_ENVS;
+}
+
+static int terrain_launch_y_field(ippm_ctx* ctx, const float2* work2, uint32_t* range_keys, uint8_t* truth, int n_envs, hipStream_t st,
+                                  int key_stride) {
+  const int gx = ctx->cfg.grid_x, gy = ctx->cfg.grid_y;
+#define LAUNCH_Y_FIELD(N1, N2, Q, ROUNDS)                                                                                      \
+  IPPM_LAUNCH(ctx, IPPM_T_TERRAIN, (k_terrain_fft_y_field<N1, N2, Q, ROUNDS>), dim3(n_envs),                                   \
+              dim3(TERRAIN_FIELD_GROUPS * FourStep<N1, N2, Q>::THREADS), st, ctx->dcfg, work2, range_keys, ctx->d_roots,       \
+              reinterpret_cast<uint32_t*>(truth), (int)(ippm_truth_bytes(gx, gy) >> 2), key_stride)
+  // (rounds = gx / (2 Q GROUPS) with Q = 16 for both sides)
+  if (gy == 128) { if (gx == 128) LAUNCH_Y_FIELD(8, 16, 16, 1); else LAUNCH_Y_FIELD(8, 16, 16, 2); }
+  else { if (gx == 128) LAUNCH_Y_FIELD(16, 16, 16, 1); else LAUNCH_Y_FIELD(16, 16, 16, 2); }
+#undef LAUNCH_Y_FIELD
+  IPPM_LAUNCH_CHECK("terrain_fft_y_field");
+  return 0;
+}
+
 extern "C" int ippm_terrain_field(ippm_ctx* ctx, const int64_t* episode, const float* amp, const float* spec, float* work,
                                   float* field, uint32_t* range_keys, int32_t n_envs, void* stream) {
   if (!ctx || !work || !field) { ippm_set_error("ippm_terrain_field: null argument"); return -1; }
@@ -599,7 +719,11 @@ extern "C" int ippm_terrain_field(ippm_ctx* ctx, const int64_t* episode, const f
 }
 
 // The episode reset's form: spectrum drawn in pass X; the field itself is never stored.  Its threshold bits need its (min, max)
-// first, so pass Y runs twice: once for the (min, max), once more (bit for bit the same transforms) for the bits.
+// first.  Fields of 128 or 256 cells a side, in batches of TERRAIN_FIELD_MIN_ENVS envs or more, take pass Y's whole-field form: one
+// workgroup per env holds all its rows in registers, so every row is transformed once and the half spectrum is read once
+// (k_terrain_fft_y_field; figures in profiles/r16/).  Larger sides (their transforms leave no registers to hold rows in) and smaller
+// batches (one workgroup per env would leave CUs empty) run pass Y twice: once for the (min, max), once more (bit for bit the same
+// transforms) for the bits.  All forms give the same truth and the same two keys, bit for bit.
 // IPPM_TERRAIN_ONE_LAUNCH=1 (round 6, measured, NOT the default): every row computed ONCE -- the workgroups of an env put their
 // (min, max) in, meet at a counter with their rows in registers and threshold them (MODE 3).  It saves the second read of the half
 // spectrum (270 MB per 1024 fields of 256^2) and the second set of transforms, and gives most of that back to workgroups that sit
@@ -615,6 +739,8 @@ extern "C" int ippm_terrain_truth(ippm_ctx* ctx, const int64_t* episode, const f
   // one counter come close to what one address takes (~12 ns each) and a wait was seen to run into its bound once in a few runs)
   if (ctx->knob_terrain_one_launch && ctx->cfg.grid_x <= 512)
     return terrain_launch_y<3>(ctx, reinterpret_cast<const float2*>(work), nullptr, range_keys, truth, n_envs, S_(stream), 4);
+  if (terrain_field_form(ctx, n_envs))
+    return terrain_launch_y_field(ctx, reinterpret_cast<const float2*>(work), range_keys, truth, n_envs, S_(stream), 4);
   if (int rc = terrain_launch_y<1>(ctx, reinterpret_cast<const float2*>(work), nullptr, range_keys, nullptr, n_envs, S_(stream), 4)) return rc;
   return terrain_launch_y<2>(ctx, reinterpret_cast<const float2*>(work), nullptr, range_keys, truth, n_envs, S_(stream), 4);
 }
