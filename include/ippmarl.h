@@ -600,6 +600,49 @@ int ippm_adam_step(void* state, float* const* params, float* const* grads, const
 int ippm_td_lambda(ippm_ctx* ctx, const float* reward, const uint8_t* done, const float* q_sel, float* td_target,
                    float* disc_return, int32_t chains, int32_t len, void* stream);
 
+/* ---- the replay buffer of the COMA round (csrc/replay.hip; batch_memory.py: add, build_td_targets, and the learners' minibatch
+ * sampling): one launch per rollout step, one per target build, one per minibatch.  The buffers are contiguous arrays in BUFFER ORDER
+ * [waves, steps, n_envs, n_agents, ...]: buf_obs float [.,11,11,7], buf_state float [.,11,11,12], buf_action int32 [.], buf_mask uint8
+ * [.,n_actions], buf_reward float [waves,steps,n_envs] (one team reward per env) or [waves,steps,n_envs,n_agents] (one per agent).  Pure
+ * data movement: every element has one owner, nothing is summed across lanes, so the results are the bytes that array-by-array copies and
+ * index operations produce.  Float and int32 arrays need 4-byte alignment only (an observation row is 3388 bytes); 16-byte accesses are
+ * taken where both addresses allow them, dword accesses otherwise.
+ *   ippm_replay_store      one rollout step.  With store != 0 the transition -- obs [E,N,11,11,7], state [E,N,11,11,12], action [E,N],
+ *                          mask [E,N,n_actions], what ippm_actor_features / ippm_critic_features / ippm_mask_act_move wrote -- is copied
+ *                          into slot (w, t) of the five buffers, and in every case the three per-env accumulators (float [E]) advance by
+ *                          exactly one float32 add each.  reward float [E,2] = (relative, absolute).  COMA form (agent_reward and
+ *                          last_agent NULL): buf_reward[w,t,e] = reward[e,0]; ret[e] += reward[e,0]; abs_ret[e] += reward[e,1];
+ *                          team_ret[e] += reward[e,0].  DeepQ form (agent_reward float [E,N,2], last_agent int32 [E], both given):
+ *                          buf_reward[w,t,e,n] = agent_reward[e,n,0]; ret[e] += agent_reward[e,last_agent[e],0]; abs_ret[e] +=
+ *                          agent_reward[e,last_agent[e],1]; team_ret[e] += reward[e,0]; a last_agent outside [0, n_agents) adds NaN to
+ *                          ret and abs_ret and reads nothing out of range.  store == 0: the accumulators only (the transition and the
+ *                          buffers may be NULL).  No context needed.
+ *   ippm_td_lambda_buffer  ippm_td_lambda (K8) on one chain per (env, agent) over all waves in time order, read from and written in buffer
+ *                          order without a transposed copy: q_sel float [waves,steps,n_envs,n_agents], reward as buf_reward above
+ *                          (reward_per_agent = 0: [waves,steps,n_envs], broadcast over the env's agents; != 0: one per agent), step
+ *                          steps - 1 of every wave is terminal -> td_target and disc_return float [waves,steps,n_envs,n_agents].  The
+ *                          per-(chain, t) arithmetic is ippm_td_lambda's own code at other strides: the same bits as ippm_td_lambda on
+ *                          the transposed arrays.
+ *   ippm_replay_gather     a minibatch: for r < count, row idx[r] (int64, device) of the buffers seen as `n` rows -> row r of states
+ *                          [count,11,11,12], obs [count,11,11,7], actions [count], masks [count,n_actions], td [count] (from buf_td float
+ *                          [n], e.g. td_target above).  Any output may be NULL and is then skipped, and its buffer may be NULL too.  Every
+ *                          index is checked in the kernel: a row with idx[r] outside [0, n) is written as zeros in every output and
+ *                          counted into bad (int32 [1], optional, never reset here); nothing outside the buffers is read.  count == 0
+ *                          launches nothing.  No context needed.
+ * -1 with ippm_last_error set for a null required pointer, n_envs or n_agents < 1, n_actions outside [1, 32], a slot outside the buffers,
+ * agent_reward without last_agent (or the reverse), a product of the dimensions of 2^31 or more (TD), n < 1, count < 0, a misaligned
+ * array; nothing is launched then.  No host synchronisation, no allocation, launches on `stream` only. */
+int ippm_replay_store(const float* obs, const float* state, const int32_t* action, const uint8_t* mask, const float* reward,
+                      const float* agent_reward, const int32_t* last_agent, int32_t n_envs, int32_t n_agents, int32_t n_actions,
+                      int32_t waves, int32_t steps, int32_t w, int32_t t, int32_t store, float* buf_obs, float* buf_state,
+                      int32_t* buf_action, uint8_t* buf_mask, float* buf_reward, float* ret, float* abs_ret, float* team_ret,
+                      void* stream);
+int ippm_td_lambda_buffer(ippm_ctx* ctx, const float* reward, int32_t reward_per_agent, const float* q_sel, float* td_target,
+                          float* disc_return, int32_t waves, int32_t steps, int32_t n_envs, int32_t n_agents, void* stream);
+int ippm_replay_gather(const float* buf_state, const float* buf_obs, const int32_t* buf_action, const uint8_t* buf_mask,
+                       const float* buf_td, int64_t n, const int64_t* idx, int64_t count, int32_t n_actions, float* states, float* obs,
+                       int32_t* actions, uint8_t* masks, float* td, int32_t* bad, void* stream);
+
 /* ---- greedy information-gain planner (IG_baseline.py:222-325) and evaluation metrics -------------------------
  * ippm_ig_candidates (K9): gains float [E,N,A] = expected weighted entropy reduction over the footprint each valid action
  * leads to, / 1000 (get_individual_ig); masked actions get 0.  ippm_ig_select (K10): get_relative_ig +

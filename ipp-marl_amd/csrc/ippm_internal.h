@@ -269,6 +269,36 @@ __device__ __forceinline__ float ippm_coma_baseline(bool on, float prob, float q
   return b;
 }
 
+// K8's (chain, t) (batch_memory.py:120-162 restated in O(len)), shared by k_td_lambda (learn.hip: chains stored [chains, len]) and
+// k_td_lambda_buffer (replay.hip: the replay buffer's [W,T,E,N] order): the n-step return grows by one reward per n, accumulation stops
+// ("leave") at the first transition whose predecessor is terminal.  r and qs point at the chain's element 0; element i is rs / qstr floats
+// further on; done(i) tells whether transition i of the chain is terminal.
+template <class Done>
+__device__ __forceinline__ void ippm_td_lambda_at(const float* __restrict__ r, size_t rs, const float* __restrict__ qs, size_t qstr,
+                                                  Done done, int t, int len, double gamma, double lam, float& td, float& dr) {
+  double total = 0.0, g = 0.0, disc = 0.0;
+  double gpow = 1.0;    // gamma^(n-1)
+  double lpow = 1.0;    // lambda^(n-1)
+  for (int n = 1; n <= len - t; ++n) {
+    const int l = n - 1;  // the new term of this n
+    const bool ok = (t + l == 0) || !done(t + l - 1);
+    if (!ok) {            // leave: weight lambda^n on the partial return, then stop
+      total += lpow * lam * g;
+      disc = g;
+      break;
+    }
+    g += gpow * (double)r[(size_t)(t + l) * rs];
+    disc = g;
+    double gn = g;
+    if (t + n < len && !(done(t + n) || (t + n + 1 >= len))) gn += gpow * gamma * (double)qs[(size_t)(t + n) * qstr];
+    total += lpow * gn;
+    gpow *= gamma;
+    lpow *= lam;
+  }
+  td = (float)((1.0 - lam) * total);
+  dr = (float)disc;
+}
+
 // Philox4x32-10 (Salmon et al., SC'11); mirrored in oracle/ipp_oracle.py::philox4x32
 struct Philox4 {
   uint32_t v[4];

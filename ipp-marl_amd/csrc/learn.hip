@@ -31,27 +31,10 @@ __global__ void k_td_lambda(const float* __restrict__ reward, const uint8_t* __r
   const float* r = reward + (size_t)ch * len;
   const uint8_t* d = done + (size_t)ch * len;
   const float* qs = q_sel + (size_t)ch * len;
-  double total = 0.0, g = 0.0, disc = 0.0;
-  double gpow = 1.0;    // gamma^(n-1)
-  double lpow = 1.0;    // lambda^(n-1)
-  for (int n = 1; n <= len - t; ++n) {
-    const int l = n - 1;  // the new term of this n
-    const bool ok = (t + l == 0) || !d[t + l - 1];
-    if (!ok) {            // leave: weight lambda^n on the partial return, then stop
-      total += lpow * lam * g;
-      disc = g;
-      break;
-    }
-    g += gpow * (double)r[t + l];
-    disc = g;
-    double gn = g;
-    if (t + n < len && !(d[t + n] || (t + n + 1 >= len))) gn += gpow * gamma * (double)qs[t + n];
-    total += lpow * gn;
-    gpow *= gamma;
-    lpow *= lam;
-  }
-  td[idx] = (float)((1.0 - lam) * total);
-  dr[idx] = (float)disc;
+  float tdv, drv;
+  ippm_td_lambda_at(r, 1, qs, 1, [d](int i) { return d[i] != 0; }, t, len, gamma, lam, tdv, drv);   // (the arithmetic: ippm_internal.h)
+  td[idx] = tdv;
+  dr[idx] = drv;
 }
 
 extern "C" int ippm_coma_advantage(ippm_ctx* ctx, const float* probs, const float* q, const uint8_t* mask,

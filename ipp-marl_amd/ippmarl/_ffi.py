@@ -128,6 +128,9 @@ PROTOTYPES = {
     "ippm_adam_state_bytes": [P, I32, P],
     "ippm_adam_init": [P, P, I32, P],
     "ippm_adam_step": [P, P, P, P, I32, C.c_double, C.c_double, C.c_double, C.c_double, I32, I32, I32, P, P],
+    "ippm_replay_store": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P],
+    "ippm_td_lambda_buffer": [P, P, I32, P, P, P, I32, I32, I32, I32, P],
+    "ippm_replay_gather": [P, P, P, P, P, I64, P, I64, I32, P, P, P, P, P, P, P],
     "ippm_ig_candidates": [P, P, P, P, P, I32, P],
     "ippm_ig_select": [P, P, P, P, I32, P, P, I32, P],
     "ippm_f1_counts": [P, P, P, I32, C.c_float, P, I32, P],

@@ -15,6 +15,7 @@ import torch
 from . import _ffi
 from . import critic_native
 from . import optim_native
+from . import replay_native
 from .actor_native import NativeActor, resolve_mode
 from .learners import ActorLearner, CriticLearner
 from .networks import ActorNetwork, CriticNetwork, epsilon_schedule, resolve_conv2_update, resolve_head_update, resolve_trunk_update
@@ -25,10 +26,16 @@ from .vec_env import VecEnv, POLICY_ARGMAX, POLICY_SAMPLE
 class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
-                 terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None,
+                 terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None, buffer: Optional[str] = None,
                  actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, adam: Optional[str] = None,
                  head_update: Optional[str] = None, conv2_update: Optional[str] = None, trunk_update: Optional[str] = None):
         self.params = params
+        # buffer: "torch" (the default: copy_, += and index operations) or "native" (replay_native.NativeReplay: one launch of libippmarl
+        # stores a rollout step's transition and advances the returns, one builds the TD targets from buffer order, one gathers a minibatch
+        # of all five training arrays); None reads IPPMARL_BUFFER.  Who writes the buf_* tensors and the returns changes, nothing they hold
+        # does.  Independent of the other switches.
+        self.buffer = replay_native.resolve_mode(buffer)
+        self._replay = None
         # adam: "torch" (torch.optim.Adam, the default) or "native" (optim_native.NativeAdam: one launch of libippmarl steps a net, clears
         # its gradients and rewrites the inference pack where one is kept -- the same kernel whether ``graphs`` is set or not); None reads
         # IPPMARL_ADAM.  Independent of the other switches.
@@ -119,6 +126,10 @@ class COMATrainer:
         self.keep_rollout_log = False
         self.last_rollout = None
         self.last_diagnostics = None
+        if self.buffer == "native":
+            self._replay = replay_native.NativeReplay(
+                self.env.ctx, (self.buf_obs, self.buf_state, self.buf_action, self.buf_mask, self.buf_reward),
+                (self.ret, self.abs_ret, self.team_ret), self.batch_number, last_agent=last if self.deepq else None)
         if self.critic_inference == "native":
             self.critic_learner.inference = self._native_critic = critic_native.NativeCritic(self.critic, self.device)
             self._native_critic.reserve(W * T * E * N)
@@ -169,6 +180,11 @@ class COMATrainer:
         obs = env.build_observations(t)
         probs = self._act(obs, eps)
         reward, done, state = env.steps(t, policy=policy, probs=probs.view(self.E, self.N, self.A))
+        if self._replay is not None:
+            # one launch: the transition into slot (w, t) and one float32 add on each of ret, abs_ret, team_ret
+            self._replay.store(w, t, obs, state, env.action, env.mask, reward, env.agent_reward if self.deepq else None, store=store)
+            # (the returned reward is read by rollout()'s log only: the DeepQ gather is spent when that log is kept)
+            return self.last_agent_reward() if self.deepq and self.keep_rollout_log else reward
         team = reward
         if self.deepq:
             reward = self.last_agent_reward()
@@ -292,6 +308,8 @@ class COMATrainer:
                 for lo in range(0, states.shape[0], chunk):
                     q, _ = target(states[lo:lo + chunk])
                     q_sel[lo:lo + chunk] = q.view(-1, self.A).gather(1, actions[lo:lo + chunk].long().view(-1, 1)).squeeze(1)
+        if self._replay is not None:
+            return self._replay.td_targets(q_sel, W)      # q_sel is in buffer order already: one launch, no permutes
         # chains: [E*N, W*T]
         q_sel = q_sel.view(W, T, E, N).permute(2, 3, 0, 1).reshape(E * N, W * T).contiguous()
         # (COMA: the env's team reward on each of its agents' chains; DeepQ: each agent's own)
@@ -366,6 +384,29 @@ class COMATrainer:
         nv = n if flying is None else int(flying.numel())
         bs = nv // self.batch_number
         closs = aloss = torch.zeros((), device=self.device)
+        # buffer="native": ONE gather per minibatch b fills output set b % 2 of the replay (states, obs, actions, masks, td), issued right
+        # before critic_learner.backward(b); the critic side (states, actions, td) and the actor side (obs, actions, masks) of minibatch b
+        # are views of that set.  Why two alternating sets are enough: set b % 2 is next written by the gather of minibatch b + 2 (or of a
+        # later data pass).  The readers of minibatch b are critic.backward(b) (its saved tensors are released inside the call),
+        # critic.apply() of b (the post-step Q of the same states; the learner drops its reference there) and actor.backward(b).  In the
+        # loop below all three are issued -- on the one stream everything here runs on -- before the gather of b + 1, hence before that of
+        # b + 2: actor.backward(b) comes first in iteration b, then gather(b + 1), critic.backward(b + 1) and the two apply() calls, none of
+        # which reads minibatch b.  The second set is what keeps minibatch b intact while b + 1 is being gathered and used beside it.
+        # A diagnostics round keeps the torch gathers for the whole round: its records hold minibatch tensors across minibatches.
+        native = self._replay is not None and not diagnostics
+        cur = [None, None]
+
+        def critic_batch(b):
+            if native:
+                cur[b % 2] = self._replay.minibatch(idx[b], b % 2)
+                return cur[b % 2][0], cur[b % 2][2], cur[b % 2][4]
+            return states[idx[b]], actions[idx[b]], td[idx[b]]
+
+        def actor_batch(b):
+            if native:
+                return cur[b % 2][1], cur[b % 2][2], cur[b % 2][3]
+            return obs[idx[b]], actions[idx[b]], masks[idx[b]]
+
         for data_pass in range(self.data_passes):
             perm = torch.randperm(nv, device=self.device) if eager else perms[data_pass]
             if flying is not None:
@@ -380,7 +421,7 @@ class COMATrainer:
             # other's, so interleaving them -- actor(b) right after critic(b) -- computes the same numbers; it lets the
             # gradient exchange of actor(b) and critic(b+1) share one all-reduce (B+1 collectives per pass, not 2B).
             idx = [perm[b * bs:(b + 1) * bs] for b in range(self.batch_number)]
-            closs = self.critic_learner.backward(states[idx[0]], actions[idx[0]], td[idx[0]])
+            closs = self.critic_learner.backward(*critic_batch(0))
             if not self._grads_checked and eager:   # once: no gradient of the attached nets lives outside the reduced buffer
                 self.reducer.check_covered()
             self.reducer(self.critic)
@@ -388,14 +429,14 @@ class COMATrainer:
             for b in range(self.batch_number):
                 if collect:
                     crit_rec.append(dict(self.critic_learner.last, discounted=dr[idx[b]]))
-                aloss, _ = self.actor_learner.backward(obs[idx[b]], actions[idx[b]], masks[idx[b]], q_b, eps)
+                aloss, _ = self.actor_learner.backward(*actor_batch(b), q_b, eps)
                 if collect:
                     act_rec.append(self.actor_learner.last)
                 if not self._grads_checked and eager:
                     self.reducer.check_covered()
                     self._grads_checked = True
                 if b + 1 < self.batch_number:
-                    closs = self.critic_learner.backward(states[idx[b + 1]], actions[idx[b + 1]], td[idx[b + 1]])
+                    closs = self.critic_learner.backward(*critic_batch(b + 1))
                     self.reducer(self.critic, self.actor)
                     self.actor_learner.apply()
                     q_b = self.critic_learner.apply()
