@@ -594,6 +594,54 @@ int ippm_adam_init(void* state, const int64_t* numel, int32_t n_tensors, void* s
 int ippm_adam_step(void* state, float* const* params, float* const* grads, const int64_t* numel, int32_t n_tensors, double lr, double beta1,
                    double beta2, double eps, int32_t flags, int32_t pack_planes, int32_t n_actions, void* packed, void* stream);
 
+/* ---- native training metrics (csrc/metrics.hip): the 32 scalars the reference logs per training step (coma_mission.py:208-424,
+ * critic/learner.py:100-190, actor/learner.py:36-200), reduced on the device from the arrays a minibatch step has anyway.  A round of
+ * n_minibatches minibatches ("slots") of `batch` rows and n_actions actions accumulates into a caller-owned blob; one closing launch
+ * writes double out[IPPM_METRICS_SCALARS] on the device, in this order:
+ *    0 critic loss mean            1 TD target mean      2 TD target std        3 chosen-Q mean       4 Q mean (post-step, all actions)
+ *    5 Q min     6 Q std           7 explained variance (y_true = disc, y_pred = td)                 8 disc. return mean    9 ... std
+ *   10 |disc - q_chosen| mean     11 ... std            12 "log probs according to critic"           13-18 critic gradient figures
+ *   19 actor loss mean            20 advantage mean     21 advantage std       22 log p(chosen) mean  23 policy entropy
+ *   24 KL figure                  25 "hidden state entropy"                    26-31 actor gradient figures
+ * Definitions (quirks of the reference included): every std is the unbiased one over all rows of all slots (one element: NaN); 7 uses
+ * population variances, and with a zero variance of disc it is 1 if the residual's variance is zero too, else 0; 12 is the mean over all
+ * rows of q_new[b,a_b] - logsumexp_{b'} q_new[b',a_b], the log-softmax over the BATCH axis of each slot; 23 is the mean over rows of
+ * -sum_a p log p (0 log 0 is NaN); 24 is (1 / (batch n_actions)) sum_{slot,b,a} p_old (log p_old - p_after), i.e. log(p_old / exp(p_after))
+ * summed over the slots and averaged over (b, a); 25 is the mean over slots of the mean square of hidden0; a gradient figure is
+ * (|g_w|_1 + |g_b|_1) / 2 for conv1, conv2, conv3, fc1, [fc2: always 0], fc3.  An action outside [0, n_actions) gives NaN in 12 and 22 and
+ * reads nothing out of range.
+ * Arithmetic contract: every element is converted to double first; log and exp are double.  A workgroup owns
+ * IPPM_METRICS_CHUNK rows of one slot; within a chunk, lane values are reduced by one fixed tree (wavefront shuffles, then LDS); moments
+ * travel as (n, sum, M2) and are merged by Chan's formula, a column's log-sum-exp as (max, sum exp(x - max)); the closing launch merges the
+ * chunks of a slot in chunk order, then the slots in slot order.  No atomics, no workgroup waits on another.  Every call overwrites all
+ * partials of its slot (grad_l1: of its net), so the blob needs no initialisation and `out` depends on the inputs, batch, n_actions and
+ * n_minibatches only -- not on the order of the calls, the grid, or what the blob held.  NaN and Inf propagate to the scalars their element
+ * enters, and to no other.
+ *   ippm_metrics_bytes        size of the blob (16-byte aligned, caller-owned).
+ *   ippm_metrics_critic       slot's critic arrays: loss float [1]; q_chosen (pre-step), td, disc float [batch]; q_new float
+ *                             [batch,n_actions] (post-step); action int32 [batch].
+ *   ippm_metrics_actor        slot's actor arrays: loss float [1]; adv float [batch]; probs float [batch,n_actions] (epsilon-mixed);
+ *                             action int32 [batch]; hidden0 float [256], the conv features of the slot's first sample.
+ *   ippm_metrics_actor_after  the KL figure's terms of a slot: probs_old as given to ippm_metrics_actor, probs_after the updated actor's.
+ *   ippm_metrics_grad_l1      the L1 norms of a net's ten gradients (net 0: critic, 1: actor); grads: a HOST array of 10 device pointers in
+ *                             the order of the Adam step's tensors (conv1.w, conv1.b, ... fc1.w, fc1.b, fc3.w, fc3.b); numel in [1, 2^36].
+ *   ippm_metrics_finalize     one workgroup: everything above -> out.
+ * -1 with ippm_last_error set for a null pointer, batch outside [2, 2^24] (at 1 the reference's squeeze() changes the softmax axis),
+ * n_actions outside [2, 32], n_minibatches outside [1, 65536], a slot outside [0, n_minibatches), a net other than 0 or 1, n_tensors other
+ * than 10, a blob that is not 16-byte aligned, an array that is not 4-byte aligned (out: 8); nothing is launched then.  No context needed, no
+ * host synchronisation, no allocation; pointers and the slot travel by value, launches on `stream` only (capturable). */
+#define IPPM_METRICS_SCALARS 32
+#define IPPM_METRICS_CHUNK 256
+int ippm_metrics_bytes(int32_t n_minibatches, int64_t batch, int32_t n_actions, int64_t* bytes);
+int ippm_metrics_critic(void* acc, int32_t slot, int32_t n_minibatches, const float* loss, const float* q_chosen, const float* td,
+                        const float* disc, const float* q_new, const int32_t* action, int64_t batch, int32_t n_actions, void* stream);
+int ippm_metrics_actor(void* acc, int32_t slot, int32_t n_minibatches, const float* loss, const float* adv, const float* probs,
+                       const int32_t* action, const float* hidden0, int64_t batch, int32_t n_actions, void* stream);
+int ippm_metrics_actor_after(void* acc, int32_t slot, int32_t n_minibatches, const float* probs_old, const float* probs_after,
+                             int64_t batch, int32_t n_actions, void* stream);
+int ippm_metrics_grad_l1(void* acc, int32_t net, float* const* grads, const int64_t* numel, int32_t n_tensors, void* stream);
+int ippm_metrics_finalize(const void* acc, int32_t n_minibatches, int64_t batch, int32_t n_actions, double* out, void* stream);
+
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
  * Q(s_t)[a_t] -> td_target, discounted_return float. */

@@ -11,6 +11,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _ffi
+from . import metrics_native
 from . import optim_native
 from .networks import conv2_update as conv2_update_mode, resolve_conv2_update
 from .networks import resolve_trunk_update, trunk_update as trunk_update_mode
@@ -36,8 +37,8 @@ def _optimizer(module, lr: float, capturable: bool, adam: str):
 
 
 class CriticLearner:
-    def __init__(self, params: Dict, critic, device, capturable: bool = False, adam: str = "torch", head_update: str = "float32",
-                 conv2_update: str = "float32", trunk_update: str = "float32"):
+    def __init__(self, params: Dict, critic, device, metrics: str = "torch", capturable: bool = False, adam: str = "torch",
+                 head_update: str = "float32", conv2_update: str = "float32", trunk_update: str = "float32"):
         self.params = params
         # the optimizer: "torch" (torch.optim.Adam), or "native" (optim_native.NativeAdam: one launch steps the net, clears its gradients
         # and, where an inference pack is kept, rewrites it)
@@ -62,6 +63,10 @@ class CriticLearner:
         self.optimizer.zero_grad()
         self.collect = False   # keep the tensors ippmarl.metrics.critic_metrics needs in self.last
         self.last = None
+        # metrics: "torch" (``collect`` and ippmarl.metrics), or "native": with ``observe`` = (NativeMetrics, slot, disc [B]) set, apply() hands
+        # the minibatch's arrays -- from whichever path produced them -- to ippm_metrics_critic; ``collect`` stays off and nothing else changes
+        self.metrics = metrics_native.resolve_mode(metrics)
+        self.observe = None
         # optional inference hook (the trainer sets a critic_native.NativeCritic of ``critic``): the post-step Q of apply() then comes
         # from its bf16 forward; None: the float32 module
         self.inference = None
@@ -97,8 +102,16 @@ class CriticLearner:
 
     def apply(self):
         """Second half: Adam step, then the POST-step Q handed to the actor (critic/learner.py:93-105).  -> q_new [B,A]"""
-        states, actions, td_targets, loss, q_chosen = self._pending
+        pending = self._pending
         self._pending = None
+        q_new = self._step_and_q(*pending)
+        if self.observe is not None:
+            states, actions, td_targets, loss, q_chosen = pending
+            sink, slot, disc = self.observe
+            sink.critic(slot, loss, q_chosen, td_targets, disc, q_new, actions)
+        return q_new
+
+    def _step_and_q(self, states, actions, td_targets, loss, q_chosen):
         if self.adam == "native" and self.inference is not None:
             self.optimizer.attach_pack(self.inference)       # the step's launch rewrites the pack: nothing to repack afterwards
             self.optimizer.step()
@@ -126,10 +139,14 @@ class CriticLearner:
 
 
 class ActorLearner:
-    def __init__(self, params: Dict, actor, device, ctx: Optional[_ffi.Context] = None, capturable: bool = False, adam: str = "torch",
-                 head_update: str = "float32", conv2_update: str = "float32", trunk_update: str = "float32"):
+    def __init__(self, params: Dict, actor, device, ctx: Optional[_ffi.Context] = None, metrics: str = "torch", capturable: bool = False,
+                 adam: str = "torch", head_update: str = "float32", conv2_update: str = "float32", trunk_update: str = "float32"):
         self.params = params
         self.adam = optim_native.resolve_mode(adam)             # as CriticLearner's
+        # as CriticLearner's: with ``observe`` = (NativeMetrics, slot) set, backward() hands loss, advantages, the pre-step probabilities and
+        # the first sample's conv features to ippm_metrics_actor
+        self.metrics = metrics_native.resolve_mode(metrics)
+        self.observe = None
         self.head_update = resolve_head_update(head_update)     # as CriticLearner's (networks._HeadBf16, _ActorLossBf16)
         self.conv2_update = resolve_conv2_update(conv2_update)   # as CriticLearner's
         self.trunk_update = resolve_trunk_update(trunk_update)
@@ -165,10 +182,14 @@ class ActorLearner:
         if self.head_update == "bf16" and not self.collect and observations.is_cuda:
             # the native head: the trunk's logits, then softmax, epsilon mix, K7, the loss and its gradient in one kernel
             with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update), head_update_mode("bf16"):
-                logits, _ = self.actor.trunk(observations)
-            loss, adv = _ActorLossBf16.apply(logits, q_values, masks, actions, eps)
+                logits, hidden = self.actor.trunk(observations)
+            sink, slot = self.observe if self.observe is not None else (None, 0)
+            # (observed: the loss kernel writes its probabilities straight into the metrics' buffer of pre-step policies)
+            loss, adv = _ActorLossBf16.apply(logits, q_values, masks, actions, eps, None if sink is None else sink.probs_old[slot])
             self.optimizer.zero_grad(set_to_none=False)
             loss.backward()
+            if sink is not None:
+                sink.actor(slot, loss.detach(), adv, sink.probs_old[slot], actions, hidden[0].detach())
             return loss.detach(), adv
         with conv2_update_mode(self.conv2_update), trunk_update_mode(self.trunk_update):
             probs, hidden = self.actor(observations, eps)
@@ -182,6 +203,9 @@ class ActorLearner:
         if self.collect:
             self.last = dict(loss=loss.detach(), adv=adv.detach(), log_probs=log_probs.detach(), log_chosen=log_chosen.detach(),
                              hidden0=hidden[0].detach())
+        if self.observe is not None:
+            sink, slot = self.observe
+            sink.actor(slot, loss.detach(), adv.detach(), probs.detach(), actions, hidden[0].detach())
         return loss.detach(), adv
 
     def apply(self):

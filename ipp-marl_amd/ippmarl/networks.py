@@ -421,10 +421,12 @@ class _CriticLossBf16(torch.autograd.Function):
 class _ActorLossBf16(torch.autograd.Function):
     """(logits [B,A], q_values, mask, action, eps) -> (loss, adv [B]) of actor/learner.py:52-97 through ippm_actor_loss: softmax, the
     epsilon mix, K7's advantage, the mask-weighted mean, and the gradient of the loss with respect to the logits in one kernel; the
-    backward scales that gradient, on the device, by the incoming one.  ``eps``: a float, or a device scalar (recorded rounds)."""
+    backward scales that gradient, on the device, by the incoming one.  ``eps``: a float, or a device scalar (recorded rounds).
+    ``probs_out`` (optional, float32 [B,A], contiguous): receives the epsilon-mixed probabilities the loss was formed from (the native
+    metrics' pre-step policy)."""
 
     @staticmethod
-    def forward(ctx, logits, q_values, mask, action, eps):
+    def forward(ctx, logits, q_values, mask, action, eps, probs_out=None):
         from . import _ffi
         lib = _ffi.load_library()
         ls, q32 = logits.detach().contiguous(), q_values.detach().float().contiguous()
@@ -435,8 +437,12 @@ class _ActorLossBf16(torch.autograd.Function):
         dlogits = torch.empty_like(ls)
         eps_dev = eps if isinstance(eps, torch.Tensor) else None
         scratch = _head_scratch(lib, B, A, ls.device, losses_only=True)
+        if probs_out is not None and (probs_out.dtype != ls.dtype or probs_out.numel() != B * A or not probs_out.is_contiguous()
+                                      or probs_out.device != ls.device):
+            raise _ffi.IppmError("_ActorLossBf16: probs_out must be a contiguous float32 [B,A] tensor on the logits' device")
         _ffi.check(lib.ippm_actor_loss(ls.data_ptr(), q32.data_ptr(), m8.data_ptr(), a32.data_ptr(), B, A, 0.0 if eps_dev is not None else float(eps),
-                                       None if eps_dev is None else eps_dev.data_ptr(), scratch.data_ptr(), loss.data_ptr(), adv.data_ptr(), None,
+                                       None if eps_dev is None else eps_dev.data_ptr(), scratch.data_ptr(), loss.data_ptr(), adv.data_ptr(),
+                                       None if probs_out is None else probs_out.data_ptr(),
                                        dlogits.data_ptr(), torch.cuda.current_stream(ls.device).cuda_stream), "ippm_actor_loss")
         ctx.save_for_backward(dlogits)
         ctx.mark_non_differentiable(adv)
@@ -445,7 +451,7 @@ class _ActorLossBf16(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss, _grad_adv):
         (dlogits,) = ctx.saved_tensors
-        return dlogits * grad_loss, None, None, None, None
+        return dlogits * grad_loss, None, None, None, None, None
 
 
 class _BiasReLU(torch.autograd.Function):

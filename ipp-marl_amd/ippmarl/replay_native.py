@@ -121,3 +121,17 @@ class NativeReplay:
                                                self.A, p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(out[4]), p(self.bad), self._stream()),
                    "ippm_replay_gather")
         return tuple(o[:count] for o in out)
+
+    def gather_values(self, values: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """``out[r] = values[idx[r]]`` for a float32 array in buffer order (the discounted returns of the native metrics): the gather launch
+        with ``values`` in the TD targets' place and every other output left out.  ``out``: a caller-owned float32 tensor of idx.numel()."""
+        count = int(idx.numel())
+        if (idx.dtype != torch.int64 or idx.device != self.device or self.rows < 1 or values.dtype != torch.float32 or values.numel() < self.rows
+                or out.dtype != torch.float32 or out.numel() != count or not out.is_contiguous()):
+            raise _ffi.IppmError("NativeReplay.gather_values: float32 values in buffer order, int64 indices and a float32 output of their "
+                                 "number are needed, after td_targets()")
+        idx = idx.contiguous()
+        p = _ffi.ptr
+        _ffi.check(self.lib.ippm_replay_gather(None, None, None, None, p(values), self.rows, p(idx), count, self.A, None, None, None, None,
+                                               p(out), p(self.bad), self._stream()), "ippm_replay_gather")
+        return out

@@ -14,6 +14,7 @@ import torch
 
 from . import _ffi
 from . import critic_native
+from . import metrics_native
 from . import optim_native
 from . import replay_native
 from .actor_native import NativeActor, resolve_mode
@@ -26,10 +27,19 @@ from .vec_env import VecEnv, POLICY_ARGMAX, POLICY_SAMPLE
 class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
-                 terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None, buffer: Optional[str] = None,
+                 terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None, metrics: Optional[str] = None,
+                 buffer: Optional[str] = None,
                  actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, adam: Optional[str] = None,
                  head_update: Optional[str] = None, conv2_update: Optional[str] = None, trunk_update: Optional[str] = None):
         self.params = params
+        # metrics: who computes the 32 per-training-step scalars of update(diagnostics=True): "torch" (the default: the learners collect
+        # per-minibatch records on the float32 path and ippmarl.metrics reduces them, launch by launch) or "native"
+        # (metrics_native.NativeMetrics: libippmarl reduces the arrays of the round AS CONFIGURED -- native head, gathers, critic forward
+        # and Adam stay on -- inside the recorded graph, read with one device-to-host copy); None reads IPPMARL_METRICS.  Independent of
+        # the other switches; metrics observe a round and never change it.
+        self.metrics = metrics_native.resolve_mode(metrics)
+        self._metrics = None
+        self._graph_metrics = False
         # buffer: "torch" (the default: copy_, += and index operations) or "native" (replay_native.NativeReplay: one launch of libippmarl
         # stores a rollout step's transition and advances the returns, one builds the TD targets from buffer order, one gathers a minibatch
         # of all five training arrays); None reads IPPMARL_BUFFER.  Who writes the buf_* tensors and the returns changes, nothing they hold
@@ -95,9 +105,11 @@ class COMATrainer:
         self.graphs = bool(graphs)
         self._step_graphs = self._update_graph = None
         self.actor_learner = ActorLearner(params, self.actor, self.device, ctx=self.env.ctx, capturable=self.graphs, adam=self.adam,
-                                          head_update=self.head_update, conv2_update=self.conv2_update, trunk_update=self.trunk_update)
+                                          head_update=self.head_update, conv2_update=self.conv2_update, trunk_update=self.trunk_update,
+                                          metrics=self.metrics)
         self.critic_learner = CriticLearner(params, self.critic, self.device, capturable=self.graphs, adam=self.adam,
-                                            head_update=self.head_update, conv2_update=self.conv2_update, trunk_update=self.trunk_update)
+                                            head_update=self.head_update, conv2_update=self.conv2_update, trunk_update=self.trunk_update,
+                                            metrics=self.metrics)
         for m in (self.actor, self.critic, self.critic_learner.target_critic, self.frozen_target):
             broadcast_module(m)
         # gradients of both nets live in one flat buffer (critic, then actor): the data-parallel average is one all-reduce of a
@@ -201,7 +213,10 @@ class COMATrainer:
 
     def _act(self, obs: torch.Tensor, eps) -> torch.Tensor:
         """probs [E*N, A] of the current actor for the observations [E,N,11,11,7], without gradients, on the selected inference path."""
-        obs = obs.view(self.E * self.N, 11, 11, 7)
+        return self._act_rows(obs.view(self.E * self.N, 11, 11, 7), eps)
+
+    def _act_rows(self, obs: torch.Tensor, eps) -> torch.Tensor:
+        """``_act`` for any number of rows [B,11,11,7] (the native metrics' post-pass forwards on the minibatches)."""
         if self.actor_inference == "native":
             return self.native_actor()(obs, eps)[0]
         with torch.no_grad():
@@ -276,12 +291,17 @@ class COMATrainer:
                 self._rollout_step(t, 0, POLICY_SAMPLE, True, self.eps_dev)
             graphs.append(g)
         n = self.T * self.E * self.N
+        # metrics="native": the metric launches and the post-pass forwards are part of the recorded round (the accumulator is allocated
+        # here, outside the capture); update(diagnostics=True) replays and reads ``out``, update(diagnostics=False) replays and reads nothing
+        self._graph_metrics = self.metrics == "native"
+        if self._graph_metrics:
+            self._native_metrics(n // self.batch_number)
         self._perms = torch.stack([torch.randperm(n, device=self.device) for _ in range(self.data_passes)])
         self._loss_out = torch.zeros(2, device=self.device)
         filled, self.filled = self.filled, 1
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=stream):
-            closs, aloss = self._update_compute(self._perms, self.eps_dev, False)
+            closs, aloss = self._update_compute(self._perms, self.eps_dev, self._graph_metrics)
             self._loss_out[0].copy_(closs)
             self._loss_out[1].copy_(aloss)
         self.filled = filled
@@ -328,12 +348,14 @@ class COMATrainer:
 
     def update(self, diagnostics: bool = False) -> Dict[str, float]:
         """One COMA round on everything in the buffer, then clear it (coma_mission.py:89-116).  ``diagnostics``: also
-        compute the reference's per-training-step TensorBoard figures from data pass 0 (ippmarl.metrics) into
-        ``self.last_diagnostics`` (costs one extra actor forward per minibatch)."""
+        compute the reference's per-training-step TensorBoard figures from data pass 0 into ``self.last_diagnostics`` (costs one extra
+        actor forward per minibatch).  metrics="torch": ippmarl.metrics on the learners' float32 records, launch by launch even when the
+        round is recorded; metrics="native": libippmarl's reductions on the round as configured, replayed with the recorded round, one
+        device-to-host read."""
         W, T, E, N = self.filled, self.T, self.E, self.N
         assert W > 0, "update() needs at least one rollout wave"
         n = W * T * E * N
-        if self._update_graph is not None and W == 1 and not diagnostics:
+        if self._update_graph is not None and W == 1 and (not diagnostics or self._graph_metrics):
             # the recorded round: hard target copy (a host-side decision) first, fresh permutations into the graph's buffer, replay
             self.critic_learner.update_target_network(self.train_step, 0)
             if self.critic_inference == "native":
@@ -344,9 +366,13 @@ class COMATrainer:
             self.train_step += 1
             self.filled = 0
             closs, aloss = self._loss_out.tolist()
+            if diagnostics:
+                self.last_diagnostics = self._metrics.read()
             return {"critic_loss": closs, "actor_loss": aloss, "transitions": n * self.world,
                     "adam_steps": 2 * self.data_passes * self.batch_number, "train_step": self.train_step}
         closs, aloss = self._update_compute(None, self.eps_dev if self.graphs else self.eps, diagnostics)
+        if diagnostics and self.metrics == "native":
+            self.last_diagnostics = self._metrics.read()
         self.filled = 0
         total = n * self.world
         if self.env.n_active is not None:
@@ -360,6 +386,15 @@ class COMATrainer:
             total = int(mine[0])
         return {"critic_loss": float(closs), "actor_loss": float(aloss), "transitions": total,
                 "adam_steps": 2 * self.data_passes * self.batch_number, "train_step": self.train_step}
+
+    def _native_metrics(self, batch: int):
+        """The NativeMetrics of a round of ``batch_number`` minibatches of ``batch`` rows (rebuilt when the minibatch size changes; a
+        recorded round holds its addresses, so there it must not)."""
+        if self._metrics is None or not self._metrics.matches(self.batch_number, batch, self.A):
+            if torch.cuda.is_current_stream_capturing() or (self._graph_metrics and self._update_graph is not None):
+                raise _ffi.IppmError("COMATrainer: the minibatch size of the recorded round's native metrics has changed")
+            self._metrics = metrics_native.NativeMetrics(self.batch_number, batch, self.A, self.device)
+        return self._metrics
 
     def valid_transitions(self, waves: int) -> Optional[torch.Tensor]:
         """Indices into the flattened [waves, T, E, N] buffers of the transitions of agents that fly (None: all of them do)."""
@@ -392,8 +427,12 @@ class COMATrainer:
         # loop below all three are issued -- on the one stream everything here runs on -- before the gather of b + 1, hence before that of
         # b + 2: actor.backward(b) comes first in iteration b, then gather(b + 1), critic.backward(b + 1) and the two apply() calls, none of
         # which reads minibatch b.  The second set is what keeps minibatch b intact while b + 1 is being gathered and used beside it.
-        # A diagnostics round keeps the torch gathers for the whole round: its records hold minibatch tensors across minibatches.
+        # A diagnostics round of metrics="torch" keeps the torch gathers for the whole round: its records hold minibatch tensors across
+        # minibatches.  metrics="native" keeps nothing (the learners hand each minibatch's arrays to the accumulator when they have them).
+        watch = diagnostics and self.metrics == "native"
+        diagnostics = diagnostics and not watch
         native = self._replay is not None and not diagnostics
+        sink = self._native_metrics(bs) if watch else None
         cur = [None, None]
 
         def critic_batch(b):
@@ -414,6 +453,16 @@ class COMATrainer:
             if eager:
                 self.critic_learner.update_target_network(self.train_step, data_pass)
             collect = diagnostics and data_pass == 0
+            observe = watch and data_pass == 0
+            last = self.batch_number - 1
+
+            def observe_critic(b):
+                # the discounted returns of minibatch b into the accumulator's own buffer (buffer="native": one more gather launch)
+                if self._replay is not None:
+                    disc = self._replay.gather_values(dr, idx[b], sink.disc[b])
+                else:
+                    disc = sink.disc[b].copy_(dr[idx[b]])
+                self.critic_learner.observe = (sink, b, disc)
             self.critic_learner.collect = self.actor_learner.collect = collect
             crit_rec, act_rec = [], []
             # Reference order (critic/learner.py:58-105, actor/learner.py:36-101): all critic minibatches, each followed by
@@ -425,10 +474,16 @@ class COMATrainer:
             if not self._grads_checked and eager:   # once: no gradient of the attached nets lives outside the reduced buffer
                 self.reducer.check_covered()
             self.reducer(self.critic)
+            if observe:
+                observe_critic(0)
+                if last == 0:
+                    sink.grad_l1(0, [p.grad for p in optim_native.used_parameters(self.critic)])
             q_b = self.critic_learner.apply()
             for b in range(self.batch_number):
                 if collect:
                     crit_rec.append(dict(self.critic_learner.last, discounted=dr[idx[b]]))
+                if observe:
+                    self.actor_learner.observe = (sink, b)
                 aloss, _ = self.actor_learner.backward(*actor_batch(b), q_b, eps)
                 if collect:
                     act_rec.append(self.actor_learner.last)
@@ -438,11 +493,23 @@ class COMATrainer:
                 if b + 1 < self.batch_number:
                     closs = self.critic_learner.backward(*critic_batch(b + 1))
                     self.reducer(self.critic, self.actor)
+                    if observe:
+                        observe_critic(b + 1)
+                        if b + 1 == last:     # the gradient figures are the last minibatch's, after the all-reduce, before the step clears them
+                            sink.grad_l1(0, [p.grad for p in optim_native.used_parameters(self.critic)])
                     self.actor_learner.apply()
                     q_b = self.critic_learner.apply()
                 else:
                     self.reducer(self.actor)
+                    if observe:
+                        sink.grad_l1(1, [p.grad for p in optim_native.used_parameters(self.actor)])
                     self.actor_learner.apply()
+            if observe:
+                # the KL figure: the updated actor on the pass's minibatches, through the configured no-grad path, then the closing launch
+                self.critic_learner.observe = self.actor_learner.observe = None
+                for b in range(self.batch_number):
+                    sink.actor_after(b, self._act_rows(obs[idx[b]], eps))
+                sink.finalize()
             if collect:
                 from . import metrics
                 with torch.no_grad():
