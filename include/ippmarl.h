@@ -642,6 +642,49 @@ int ippm_metrics_actor_after(void* acc, int32_t slot, int32_t n_minibatches, con
 int ippm_metrics_grad_l1(void* acc, int32_t net, float* const* grads, const int64_t* numel, int32_t n_tensors, void* stream);
 int ippm_metrics_finalize(const void* acc, int32_t n_minibatches, int64_t batch, int32_t n_actions, double* out, void* stream);
 
+/* ---- native rollout log (csrc/rollout_log.hip): the per-round return / reward statistics and the action and altitude histograms the
+ * reference logs beside the training metrics (coma_mission.py:174-267).  One launch per rollout step writes that step's share of n_waves
+ * waves of n_steps steps of n_envs envs into a caller-owned blob; one closing launch writes, on the device,
+ *   double out[IPPM_ROLLOUT_SCALARS]: mean, population std (np.std), max, min of
+ *      0-3  the absolute episode returns (n_waves n_envs values)
+ *      4-7  the per-step relative rewards (n_waves n_steps n_envs values)
+ *      8-11 the relative episode returns (n_waves n_envs values)
+ *   int64 counts[IPPM_ROLLOUT_COUNTS]: [0,32) actions flown, [32,64) altitude levels reached, [64] entries counted in no bin.
+ * Arithmetic contract: the step call stores both reward columns of its (wave, step) slot as float32.  An episode's
+ * return is the float32 sum of its step rewards in step order, starting from the first one -- the adds of ippm_replay_store, bit for bit,
+ * so max and min of a return series are exactly those of the accumulators.  Statistics convert every element to double first; a thread of
+ * the closing workgroup forms the moments (n, sum, M2) of its max(2, ceil(episodes / 256) rounded up to even) consecutive episodes
+ * (wave-major, then env) in two passes, and the 256 shares are merged by Chan's formula in one fixed tree (neighbours first over the
+ * wavefront, then the four wavefronts in order): an order that depends on the sizes only.  One element gives std 0.  No floating-point
+ * atomics, no workgroup waits on another.  NaN and Inf reach all four scalars of the series they enter (max and min keep a NaN as np.max
+ * and np.min do) and no other series, and never the counts.  Counts are exact integers, one set of bins per workgroup of
+ * IPPM_ROLLOUT_ROWS (env, agent) rows (wavefront ballots, then integer adds in LDS), summed in int64 by the closing launch: an agent a >=
+ * n_active[e] is counted nowhere; a flying agent adds one entry per histogram: its action to bin action if that is in [0, n_actions), else
+ * to counts[64]; its altitude to bin 32 + (z - min_altitude) / spacing if that is an integer in [0, n_levels), else to counts[64]; nothing
+ * is read or written out of range for either.  Every step call overwrites everything of its slot that is ever read, so the blob needs no
+ * initialisation and the result depends on the inputs and the sizes only -- not on the order of the calls, the grid, or what the blob
+ * held.  The blob is wave-major and a slot's place does not depend on n_waves: the closing call may name fewer waves than the blob was
+ * sized for and reduces those first waves.
+ *   ippm_rollout_log_bytes     size of the blob (16-byte aligned, caller-owned).
+ *   ippm_rollout_log_step      slot (wave, step): reward float [n_envs,2] = (relative, absolute); agent_reward NULL, or float
+ *                              [n_envs,n_agents,2] (DeepQ): the row of the LAST FLYING agent (n_active[e] - 1, or n_agents - 1; clamped
+ *                              into the table) replaces reward[e]; action int32 [n_envs,n_agents]; pos int32 [n_envs,n_agents,3] with
+ *                              pos[..,2] the altitude in metres after the move; n_active NULL (all fly) or int32 [n_envs].
+ *   ippm_rollout_log_finalize  one workgroup: the first n_waves waves -> out, counts.
+ * -1 with ippm_last_error set for a null required pointer, n_envs outside [1, 2^20], n_agents outside [1, 32], n_actions outside [2, 32],
+ * n_levels outside [1, 32], spacing < 1, n_steps or n_waves outside [1, 4096], wave or step out of range, a blob that is not 16-byte
+ * aligned, an array that is not 4-byte aligned (out, counts: 8); nothing is launched then.  No context needed, no host synchronisation, no
+ * allocation; pointers and indices travel by value, launches on `stream` only (capturable). */
+#define IPPM_ROLLOUT_SCALARS 12
+#define IPPM_ROLLOUT_COUNTS 65
+#define IPPM_ROLLOUT_ROWS 1024
+int ippm_rollout_log_bytes(int32_t n_waves, int32_t n_steps, int32_t n_envs, int32_t n_agents, int64_t* bytes);
+int ippm_rollout_log_step(void* log, int32_t wave, int32_t step, int32_t n_waves, int32_t n_steps, const float* reward,
+                          const float* agent_reward, const int32_t* action, const int32_t* pos, const int32_t* n_active, int32_t n_envs,
+                          int32_t n_agents, int32_t n_actions, int32_t min_altitude, int32_t spacing, int32_t n_levels, void* stream);
+int ippm_rollout_log_finalize(const void* log, int32_t n_waves, int32_t n_steps, int32_t n_envs, int32_t n_agents, double* out,
+                              int64_t* counts, void* stream);
+
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
  * Q(s_t)[a_t] -> td_target, discounted_return float. */

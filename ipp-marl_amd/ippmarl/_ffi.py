@@ -137,6 +137,9 @@ PROTOTYPES = {
     "ippm_metrics_actor_after": [P, I32, I32, P, P, I64, I32, P],
     "ippm_metrics_grad_l1": [P, I32, P, P, I32, P],
     "ippm_metrics_finalize": [P, I32, I64, I32, P, P],
+    "ippm_rollout_log_bytes": [I32, I32, I32, I32, P],
+    "ippm_rollout_log_step": [P, I32, I32, I32, I32, P, P, P, P, P, I32, I32, I32, I32, I32, I32, P],
+    "ippm_rollout_log_finalize": [P, I32, I32, I32, I32, P, P, P],
     "ippm_ig_candidates": [P, P, P, P, P, I32, P],
     "ippm_ig_select": [P, P, P, P, I32, P, P, I32, P],
     "ippm_f1_counts": [P, P, P, I32, C.c_float, P, I32, P],

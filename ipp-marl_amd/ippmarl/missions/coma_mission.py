@@ -37,23 +37,42 @@ class COMAMission(Mission):
         self.n_envs = n_envs or max(1, math.ceil(self.batch_size * self.batch_number / per_episode))
         self.trainer = COMATrainer(params, self.n_envs, device=device, **trainer_kwargs)
         self.trainer.keep_rollout_log = True
-        self.log_dir = log_dir
         self.eval_every, self.eval_episodes = eval_every, eval_episodes
+        # (rollout_log="native": the device log holds a round's train waves or one evaluation's eval waves, whichever are more)
+        self.trainer.rollout_log_waves = max(self.trainer.waves_per_update, self._eval_waves())
+        self.log_dir = log_dir
         self.training_step_idx = 0
         self.environment_step_idx = 0
         self.episode_returns = []
         self.mode = "train"
         self.last_counts = None
 
+    def _eval_waves(self) -> int:
+        return max(1, math.ceil(self.eval_episodes / self.n_envs))
+
     # ------------------------------------------------------------------------------------------------
     def add_to_tensorboard(self, rollouts, diagnostics=None):
         """coma_mission.py:174-424: return / reward statistics of the episodes since the last log (+ learner diagnostics in
-        train mode), under the reference's tags."""
+        train mode), under the reference's tags.  With the trainer's rollout_log="native" the statistics and the counts come from the
+        device log (one closing launch, one device-to-host copy) and ``rollouts`` only says how many waves there were."""
+        if self.trainer.rollout_log == "native":
+            return self._native_to_tensorboard(len(rollouts), diagnostics)
         cat = lambda key: torch.cat([r[key].flatten() for r in rollouts]).cpu()  # noqa: E731
         actions, altitudes = cat("actions"), cat("altitudes")
         self.last_counts = {"actions": [int((actions == a).sum()) for a in range(self.n_actions)],
                             "altitudes": {int(z): int((altitudes == z).sum()) for z in torch.unique(altitudes)}}
         scalars = metrics.return_scalars(self.mode, cat("absolute_returns"), cat("rewards"), cat("episode_returns"))
+        if self.mode == "train" and diagnostics:
+            scalars.update(diagnostics)
+        if self.writer is not None:
+            for tag, value in scalars.items():
+                self.writer.add_scalar(tag, value, self.training_step_idx)
+        return scalars
+
+    def _native_to_tensorboard(self, n_waves: int, diagnostics=None):
+        """add_to_tensorboard from the trainer's device log of the last ``n_waves`` waves: the same tags, the same ``last_counts``."""
+        scalars, actions, altitudes, _ = self.trainer.read_rollout_log(self.mode, n_waves)
+        self.last_counts = {"actions": actions, "altitudes": altitudes}
         if self.mode == "train" and diagnostics:
             scalars.update(diagnostics)
         if self.writer is not None:
@@ -77,18 +96,18 @@ class COMAMission(Mission):
         for _ in range(self.num_episodes):
             rollouts = []
             for _ in range(tr.waves_per_update):
-                tr.rollout("train")
+                wave = tr.rollout("train")
                 rollouts.append(tr.last_rollout)
             stats = tr.update(diagnostics=self.writer is not None)
             self.training_step_idx = tr.train_step
             self.environment_step_idx += stats["transitions"]
             self.add_to_tensorboard(rollouts, tr.last_diagnostics)
-            self.episode_returns.append(float(rollouts[-1]["episode_returns"].mean()))
+            self.episode_returns.append(wave["episode_return"])
             self.save_best_model(tr.actor)
             if self.eval_every and self.training_step_idx % self.eval_every == 0:
                 self.mode = "eval"
                 evals = []
-                for _ in range(max(1, math.ceil(self.eval_episodes / self.n_envs))):
+                for _ in range(self._eval_waves()):
                     tr.rollout("eval")
                     evals.append(tr.last_rollout)
                 self.add_to_tensorboard(evals)

@@ -17,6 +17,7 @@ from . import critic_native
 from . import metrics_native
 from . import optim_native
 from . import replay_native
+from . import rollout_native
 from .actor_native import NativeActor, resolve_mode
 from .learners import ActorLearner, CriticLearner
 from .networks import ActorNetwork, CriticNetwork, epsilon_schedule, resolve_conv2_update, resolve_head_update, resolve_trunk_update
@@ -27,7 +28,8 @@ from .vec_env import VecEnv, POLICY_ARGMAX, POLICY_SAMPLE
 class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
-                 terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None, metrics: Optional[str] = None,
+                 terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None,
+                 rollout_log: Optional[str] = None, metrics: Optional[str] = None,
                  buffer: Optional[str] = None,
                  actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, adam: Optional[str] = None,
                  head_update: Optional[str] = None, conv2_update: Optional[str] = None, trunk_update: Optional[str] = None):
@@ -46,6 +48,18 @@ class COMATrainer:
         # does.  Independent of the other switches.
         self.buffer = replay_native.resolve_mode(buffer)
         self._replay = None
+        # rollout_log: who computes the per-round rollout log a trainer with ``keep_rollout_log`` keeps (the mission's return / reward
+        # statistics and its action and altitude counts): "torch" (the default: three clones per step into ``last_rollout``, launch by
+        # launch -- such a trainer never replays its recorded rollout -- and host reductions by the caller) or "native"
+        # (rollout_native.NativeRolloutLog: one launch of libippmarl per rollout step, recorded into every step graph, so the recorded
+        # rollout replays whether the log is kept or not; read_rollout_log() closes it with one launch and one device-to-host copy, and
+        # ``last_rollout`` is not filled); None reads IPPMARL_ROLLOUT_LOG.  Independent of the other switches; the log observes a rollout
+        # and never changes it.
+        self.rollout_log = rollout_native.resolve_mode(rollout_log)
+        self._rollout_log = None
+        self.rollout_log_waves = None     # waves the native log holds (None: waves_per_update); set it before the first logged rollout
+        self.eval_wave = 0                # the native log's slot of the next eval wave; read_rollout_log("eval", ...) rewinds it
+        self.step_replays = 0             # recorded rollout steps replayed so far
         # adam: "torch" (torch.optim.Adam, the default) or "native" (optim_native.NativeAdam: one launch of libippmarl steps a net, clears
         # its gradients and rewrites the inference pack where one is kept -- the same kernel whether ``graphs`` is set or not); None reads
         # IPPMARL_ADAM.  Independent of the other switches.
@@ -136,6 +150,7 @@ class COMATrainer:
         self.abs_ret = torch.zeros(E, device=dev)
         self.team_ret = torch.zeros(E, device=dev)   # the COMA team reward summed (= ret unless DeepQ)
         self.keep_rollout_log = False
+        self._log_wave = None             # slot of the native rollout log the current wave's steps write (None: no log launch)
         self.last_rollout = None
         self.last_diagnostics = None
         if self.buffer == "native":
@@ -161,22 +176,30 @@ class COMATrainer:
         self.team_ret.zero_()
         policy = POLICY_ARGMAX if mode == "eval" else POLICY_SAMPLE
         step_rewards, step_actions, step_altitudes = [], [], []
-        replay = self._step_graphs is not None and mode == "train" and w == 0 and not self.keep_rollout_log
+        native_log = self.rollout_log == "native" and self.keep_rollout_log
+        replay = self._step_graphs is not None and mode == "train" and w == 0 and (native_log or not self.keep_rollout_log)
+        # (the native log's slot: train waves follow the buffer's, eval waves their own counter)
+        self._log_wave = (w if mode == "train" else self.eval_wave) if native_log else None
         if replay and self.actor_inference == "native":
             self.native_actor().sync()    # (weights written from the host since the last pack: the recorded steps read the pack)
         for t in range(self.T):
             if replay:
                 self._step_graphs[t].replay()
+                self.step_replays += 1
                 # (the host-side bookkeeping of the env that a replayed step skips: the step counter, no fusion pending, the
                 #  observations held are those of step t)
                 env.t, env._pending_t, env._obs_t = t + 1, None, t
                 continue
             reward = self._rollout_step(t, w, policy, mode == "train", self.eps_dev if self.graphs else self.eps)
-            if self.keep_rollout_log:
+            if self.keep_rollout_log and not native_log:
                 step_rewards.append(reward[:, 0].clone())
                 step_actions.append(env.action.clone())
                 step_altitudes.append(env.pos[:, :, 2].clone())
-        if self.keep_rollout_log:   # per-episode figures for the mission log (coma_mission.py:78-82)
+        if native_log:
+            self._log_wave = None
+            if mode == "eval":
+                self.eval_wave += 1
+        elif self.keep_rollout_log:   # per-episode figures for the mission log (coma_mission.py:78-82)
             self.last_rollout = dict(episode_returns=ret.clone(), absolute_returns=abs_ret.clone(),
                                      rewards=torch.stack(step_rewards, 1), actions=torch.stack(step_actions, 1),
                                      altitudes=torch.stack(step_altitudes, 1))
@@ -195,8 +218,13 @@ class COMATrainer:
         if self._replay is not None:
             # one launch: the transition into slot (w, t) and one float32 add on each of ret, abs_ret, team_ret
             self._replay.store(w, t, obs, state, env.action, env.mask, reward, env.agent_reward if self.deepq else None, store=store)
+            if self._log_wave is not None:
+                self._log_step(t, reward)
+                return reward
             # (the returned reward is read by rollout()'s log only: the DeepQ gather is spent when that log is kept)
             return self.last_agent_reward() if self.deepq and self.keep_rollout_log else reward
+        if self._log_wave is not None:
+            self._log_step(t, reward)
         team = reward
         if self.deepq:
             reward = self.last_agent_reward()
@@ -210,6 +238,39 @@ class COMATrainer:
         self.abs_ret += reward[:, 1]
         self.team_ret += team[:, 0]
         return reward
+
+    def _log_step(self, t: int, reward: torch.Tensor):
+        """Step ``t``'s share of the native rollout log into slot (``_log_wave``, t): one launch on the current stream, after env.steps.
+        DeepQ hands over the per-agent rewards (the kernel takes the last flying agent's row) instead of spending the gather."""
+        env = self.env
+        self.native_rollout_log().step(self._log_wave, t, reward, env.agent_reward if self.deepq else None, env.action, env.pos,
+                                       env.n_active)
+
+    def native_rollout_log(self):
+        """The NativeRolloutLog of this trainer (built on first use, for ``rollout_log_waves`` waves; the recorded steps hold its
+        addresses, so it is never rebuilt)."""
+        if self._rollout_log is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise _ffi.IppmError("COMATrainer: the native rollout log must be allocated before a capture")
+            d = self.env.d
+            waves = max(int(self.rollout_log_waves or 0), self.waves_per_update, 1)
+            self._rollout_log = rollout_native.NativeRolloutLog(waves, self.T, self.E, self.N, self.A, d.min_altitude, d.spacing, d.space_z,
+                                                                self.device)
+        return self._rollout_log
+
+    def read_rollout_log(self, mode: str = "train", n_waves: int = 1):
+        """The native rollout log of the last ``n_waves`` logged waves of ``mode`` (slots 0 .. n_waves - 1: a round's train waves, or the
+        eval waves since the last read): the closing launch and ONE device-to-host copy -> (scalars under the reference's ``mode``-prefixed
+        tags, action counts, {altitude in metres: count}, entries counted in no bin)."""
+        if self.rollout_log != "native":
+            raise _ffi.IppmError('read_rollout_log needs COMATrainer(rollout_log="native")')
+        log = self.native_rollout_log()
+        if not 1 <= n_waves <= log.W:
+            raise _ffi.IppmError(f"read_rollout_log: n_waves must be in [1, {log.W}] (rollout_log_waves), got {n_waves}")
+        log.finalize(n_waves)
+        if mode == "eval":
+            self.eval_wave = 0
+        return log.read(mode)
 
     def _act(self, obs: torch.Tensor, eps) -> torch.Tensor:
         """probs [E*N, A] of the current actor for the observations [E,N,11,11,7], without gradients, on the selected inference path."""
@@ -285,11 +346,17 @@ class COMATrainer:
                  + (("agent_reward", "agent_sums") if env.agent_rewards else ())}
         stream = torch.cuda.Stream(device=self.device)
         graphs = []
+        # rollout_log="native": the log launch rides in every recorded step, logged or not (the log is allocated here, outside the capture)
+        self._log_wave = None
+        if self.rollout_log == "native":
+            self.native_rollout_log()
+            self._log_wave = 0
         for t in range(self.T):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=stream):
                 self._rollout_step(t, 0, POLICY_SAMPLE, True, self.eps_dev)
             graphs.append(g)
+        self._log_wave = None
         n = self.T * self.E * self.N
         # metrics="native": the metric launches and the post-pass forwards are part of the recorded round (the accumulator is allocated
         # here, outside the capture); update(diagnostics=True) replays and reads ``out``, update(diagnostics=False) replays and reads nothing
