@@ -4,8 +4,8 @@
 // products accumulate in float32 on mfma_f32_16x16x32_bf16, outputs are float32 and are not rounded again.  No float atomics; every
 // output element has one owner and a fixed summation order, so a result depends on the inputs and the batch size only.
 //
-// Forward and input gradient are ONE implicit-GEMM kernel (k_conv4x4) on the tile of the inference layers (ippm_bf16_net.h: 128 rows x
-// 128 channels, K steps of 64 through LDS, lt_mma_step): out[m][n] = sum over taps, channels of in[row(m) + tap offset][ch] * W[n][tap][ch].
+// Forward and input gradient are ONE implicit-GEMM kernel (k_conv4x4) on the tile of the inference layers (ippm_bf16_tile.h: 128 rows x
+// 128 channels, K steps of 64 through LDS, lt_k_loop): out[m][n] = sum over taps, channels of in[row(m) + tap offset][ch] * W[n][tap][ch].
 //   forward         m = (sample, oy, ox), every tap, W = [o][tap][c].
 //   input gradient  a gather: gx[b,iy,ix,c] = sum over the taps (ty,tx) with (iy-ty, ix-tx) inside the output, and over o, of
 //                   gy[b,iy-ty,ix-tx,o] * w[o,c,ty,tx].  Rows are position-major: the 128 rows of a tile are 128 samples at ONE input
@@ -14,7 +14,7 @@
 // Weight gradient: gw[o,c,ty,tx] = sum over r = (b,oy,ox) of gy[r][o] * x[r + tap][c].  The reduction runs over the ROW index of both
 // operands, so both tiles go into LDS transposed ([channel][r]; the 16-byte fragment reads stay as they are).  The batch is cut into
 // chunks of IPPM_CONV4X4_WGRAD_CHUNK samples; a workgroup owns one (chunk, tap, 128 c, 128 o) tile and writes its float32 partial sums
-// to the scratch; k_conv4x4_wgrad_sum adds the partials in chunk order and writes PyTorch's [O,C,4,4] layout.
+// to the scratch; k_partial_sum<C4SumMap> adds the partials in chunk order and writes PyTorch's [O,C,4,4] layout.
 #include "ippm_bf16_net.h"
 
 namespace {
@@ -22,7 +22,6 @@ namespace {
 constexpr int C4_CH = 256;                                  // input and output channels
 constexpr int64_t C4_W = (int64_t)C4_CH * AI_K2;            // elements of one weight pack / of one chunk's partial sums
 constexpr int64_t C4_PACKS_BYTES = 2 * C4_W * 2;            // [o][tap][c] for the forward, then [c][tap][o] for the input gradient
-constexpr int64_t C4_MAX_BATCH = (int64_t)1 << 24;          // keeps every grid below 2^31 workgroups
 
 struct C4Geom { int ih, iw, oh, ow; };
 
@@ -35,14 +34,11 @@ __global__ void __launch_bounds__(256) k_conv4x4_pack(const float* __restrict__ 
   packed[i] = ai_bf16(w[(o * C4_CH + c) * 16 + tap]);
 }
 
-__device__ __forceinline__ u32x4 c4_round8(const float4& lo, const float4& hi) {
-  return u32x4{(uint32_t)ai_bf16(lo.x) | ((uint32_t)ai_bf16(lo.y) << 16), (uint32_t)ai_bf16(lo.z) | ((uint32_t)ai_bf16(lo.w) << 16),
-               (uint32_t)ai_bf16(hi.x) | ((uint32_t)ai_bf16(hi.y) << 16), (uint32_t)ai_bf16(hi.z) | ((uint32_t)ai_bf16(hi.w) << 16)};
-}
-
 // ---- forward / input gradient ------------------------------------------------------------------------------------------------------
 // BWD false: in = x [B,ih,iw,256], out = y [B,oh,ow,256], grid.x = tiles of 128 of the B*oh*ow rows.
 // BWD true:  in = gy [B,oh,ow,256], out = gx [B,ih,iw,256], grid.x = (tile of 128 samples) * ih*iw + input position.
+// The K loop and the store are written out here: on lt_k_loop and lt_for_outputs the input gradient measured 1 to 3 % slower
+// (profiles/r20/README.md); the instruction stream of this form is the one measured before the tile header existed.
 template <bool BWD>
 __global__ void __launch_bounds__(256)
 k_conv4x4(const float* __restrict__ in, const uint16_t* __restrict__ w, float* __restrict__ out, int64_t B, C4Geom g) {
@@ -111,16 +107,13 @@ k_conv4x4(const float* __restrict__ in, const uint16_t* __restrict__ w, float* _
   auto stage = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      *reinterpret_cast<u32x4*>(&As[(sr + 32 * i) * LT_LD + sc * 8]) = c4_round8(a_lo[i], a_hi[i]);
+      *reinterpret_cast<u32x4*>(&As[(sr + 32 * i) * LT_LD + sc * 8]) = lt_round8({a_lo[i].x, a_lo[i].y, a_lo[i].z, a_lo[i].w, a_hi[i].x, a_hi[i].y, a_hi[i].z, a_hi[i].w});
       *reinterpret_cast<u32x4*>(&Ws[(sr + 32 * i) * LT_LD + sc * 8]) = w_reg[i];
     }
   };
 
   floatx4 acc[4][4];   // [n tile][m tile]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
+  lt_zero(acc);
 
   const int fr = lane & 15, fk = (lane >> 4) * 8;
   const int nsteps = __popc(taps) * (C4_CH / LT_K);         // (every position has a tap inside: nsteps >= 4)
@@ -163,7 +156,7 @@ __global__ void __launch_bounds__(256)
 k_conv4x4_wgrad(const float* __restrict__ gy, const float* __restrict__ x, float* __restrict__ partial, int64_t B, C4Geom g) {
   __shared__ __attribute__((aligned(16))) uint16_t Xs[LT_M * LT_LD];   // [c][r]
   __shared__ __attribute__((aligned(16))) uint16_t Gs[LT_N * LT_LD];   // [o][r]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, wave = tid >> 6;
   const int64_t chunk = blockIdx.x >> 6;
   const int tile = blockIdx.x & 63, tap = tile >> 2, c0 = ((tile >> 1) & 1) * LT_M, o0 = (tile & 1) * LT_N;
   const int ty = tap >> 2, tx = tap & 3;
@@ -177,8 +170,8 @@ k_conv4x4_wgrad(const float* __restrict__ gy, const float* __restrict__ x, float
 
   const int rg = tid & 7, c4 = (tid >> 3) * 4;              // rows rg*8 .. rg*8+7 of the step, channels c4 .. c4+3 of the tile
   float4 xr[8], gr[8];
-  auto load = [&](int k0) __attribute__((always_inline)) {
-    const int r0 = k0 + rg * 8;
+  auto load = [&](int s) __attribute__((always_inline)) {
+    const int r0 = s * LT_K + rg * 8;
     int b = r0 / OP, p = r0 - b * OP, oy = p / g.ow, ox = p - oy * g.ow;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -198,87 +191,57 @@ k_conv4x4_wgrad(const float* __restrict__ gy, const float* __restrict__ x, float
     const float* gf = reinterpret_cast<const float*>(gr);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      uint32_t hx[8], hg[8];
+      float hx[8], hg[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { hx[j] = ai_bf16(xf[j * 4 + q]); hg[j] = ai_bf16(gf[j * 4 + q]); }
-      *reinterpret_cast<u32x4*>(&Xs[(c4 + q) * LT_LD + rg * 8]) =
-          u32x4{hx[0] | (hx[1] << 16), hx[2] | (hx[3] << 16), hx[4] | (hx[5] << 16), hx[6] | (hx[7] << 16)};
-      *reinterpret_cast<u32x4*>(&Gs[(c4 + q) * LT_LD + rg * 8]) =
-          u32x4{hg[0] | (hg[1] << 16), hg[2] | (hg[3] << 16), hg[4] | (hg[5] << 16), hg[6] | (hg[7] << 16)};
+      for (int j = 0; j < 8; ++j) { hx[j] = xf[j * 4 + q]; hg[j] = gf[j * 4 + q]; }
+      *reinterpret_cast<u32x4*>(&Xs[(c4 + q) * LT_LD + rg * 8]) = lt_round8(hx);
+      *reinterpret_cast<u32x4*>(&Gs[(c4 + q) * LT_LD + rg * 8]) = lt_round8(hg);
     }
   };
 
   floatx4 acc[4][4];   // [o tile][c tile]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
+  lt_zero(acc);
+  lt_k_loop<LT_GUARDED, LT_FREE>((R + LT_K - 1) / LT_K, load, stage, Xs, Gs, wm, wn, acc);
 
-  const int fr = lane & 15, fk = (lane >> 4) * 8;
-  load(0);
-  for (int k0 = 0; k0 < R; k0 += LT_K) {
-    __syncthreads();
-    stage();
-    __syncthreads();
-    if (k0 + LT_K < R) load(k0 + LT_K);
-    lt_mma_step(Xs, Gs, wm, wn, fr, fk, acc);
-  }
-
-  // D[o][c]: lane holds c = lane & 15 and o = (lane >> 4) * 4 + reg; partial [chunk][tap][c][o]
+  // m is c, n is o; partial [chunk][tap][c][o]
   float* pt = partial + (chunk * 16 + tap) * (int64_t)(C4_CH * C4_CH);
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int c = c0 + wm + mt * 16 + fr;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const int o = o0 + wn + nt * 16 + (lane >> 4) * 4;
-      *reinterpret_cast<float4*>(pt + c * C4_CH + o) = float4{acc[nt][mt][0], acc[nt][mt][1], acc[nt][mt][2], acc[nt][mt][3]};
-    }
-  }
+  auto row = [&](int ml) __attribute__((always_inline)) { return pt + (c0 + wm + ml) * C4_CH; };
+  lt_for_outputs(acc, row, [&](float* prow, int nl, const float4& v) __attribute__((always_inline)) {
+    *reinterpret_cast<float4*>(prow + (o0 + wn + nl)) = v;
+  });
 }
 
-// gw[o][c][tap] = the partials [chunk][tap][c][o] added in chunk order; one thread per element, reads coalesced over o
-__global__ void __launch_bounds__(256)
-k_conv4x4_wgrad_sum(const float* __restrict__ partial, int64_t chunks, float* __restrict__ gw) {
-  const int i = blockIdx.x * 256 + threadIdx.x;             // < C4_W: (tap, c, o)
-  float s = 0.f;
-  for (int64_t k = 0; k < chunks; ++k) s += partial[k * C4_W + i];
-  const int o = i & 255, c = (i >> 8) & 255, tap = i >> 16;
-  gw[(o * C4_CH + c) * 16 + tap] = s;
-}
+// gw[o][c][tap] from element i = (tap, c, o) of the partials [chunk][tap][c][o]: the reads are coalesced over o
+struct C4SumMap {
+  static constexpr int64_t STRIDE = C4_W;
+  static __device__ int out(int i) { return ((i & 255) * C4_CH + ((i >> 8) & 255)) * 16 + (i >> 16); }
+};
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
 bool c4_shape_ok(const char* who, int64_t batch, int32_t ih, int32_t iw) {
-  if (batch < 1 || batch > C4_MAX_BATCH) { ippm_set_error(std::string(who) + ": batch must be in [1, 2^24]"); return false; }
+  if (!lt_batch_ok(who, batch)) return false;
   if (ih < 4 || ih > 11 || iw < 4 || iw > 11) { ippm_set_error(std::string(who) + ": ih and iw must be in [4, 11]"); return false; }
   return true;
 }
 
-bool c4_args_ok(const char* who, const void* a, const void* b, const void* out, const void* scratch, int64_t batch, int32_t ih, int32_t iw) {
-  if (!a || !b || !out || !scratch) { ippm_set_error(std::string(who) + ": null argument"); return false; }
-  if (!c4_shape_ok(who, batch, ih, iw)) return false;
-  if (reinterpret_cast<uintptr_t>(scratch) & 15) { ippm_set_error(std::string(who) + ": scratch must be 16-byte aligned"); return false; }
-  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) & 15) {
-    ippm_set_error(std::string(who) + ": the tensors must be 16-byte aligned");
-    return false;
-  }
-  return true;
+// the three passes: two tensors in, one out, the scratch
+bool c4_pass_ok(const char* who, const void* a, const void* b, const void* out, const void* scratch, int64_t batch, int32_t ih, int32_t iw) {
+  return lt_args_ok(who, {a, b, out, scratch}, [&] { return c4_shape_ok(who, batch, ih, iw); }, {scratch}, "scratch") &&
+         lt_aligned_ok(who, {a, b, out}, "the tensors");
 }
-
-int64_t c4_chunks(int64_t batch) { return (batch + IPPM_CONV4X4_WGRAD_CHUNK - 1) / IPPM_CONV4X4_WGRAD_CHUNK; }
 
 }  // namespace
 
 extern "C" int ippm_conv4x4_bf16_scratch_bytes(int64_t batch, int32_t ih, int32_t iw, int64_t* bytes) {
   if (!bytes) { ippm_set_error("ippm_conv4x4_bf16_scratch_bytes: null argument"); return -1; }
   if (!c4_shape_ok("ippm_conv4x4_bf16_scratch_bytes", batch, ih, iw)) return -1;
-  *bytes = C4_PACKS_BYTES + c4_chunks(batch) * C4_W * 4;
+  *bytes = C4_PACKS_BYTES + lt_ceil_div(batch, IPPM_CONV4X4_WGRAD_CHUNK) * C4_W * 4;
   return 0;
 }
 
 extern "C" int ippm_conv4x4_bf16_forward(const float* x, const float* w, int64_t batch, int32_t ih, int32_t iw, void* scratch, float* y,
                                          void* stream) {
-  if (!c4_args_ok("ippm_conv4x4_bf16_forward", x, w, y, scratch, batch, ih, iw)) return -1;
+  if (!c4_pass_ok("ippm_conv4x4_bf16_forward", x, w, y, scratch, batch, ih, iw)) return -1;
   hipStream_t s = S_(stream);
   const C4Geom g = {ih, iw, ih - 3, iw - 3};
   uint16_t* pack = static_cast<uint16_t*>(scratch);
@@ -291,7 +254,7 @@ extern "C" int ippm_conv4x4_bf16_forward(const float* x, const float* w, int64_t
 
 extern "C" int ippm_conv4x4_bf16_grad_input(const float* gy, const float* w, int64_t batch, int32_t ih, int32_t iw, void* scratch, float* gx,
                                             void* stream) {
-  if (!c4_args_ok("ippm_conv4x4_bf16_grad_input", gy, w, gx, scratch, batch, ih, iw)) return -1;
+  if (!c4_pass_ok("ippm_conv4x4_bf16_grad_input", gy, w, gx, scratch, batch, ih, iw)) return -1;
   hipStream_t s = S_(stream);
   const C4Geom g = {ih, iw, ih - 3, iw - 3};
   uint16_t* pack = static_cast<uint16_t*>(scratch) + C4_W;
@@ -304,13 +267,13 @@ extern "C" int ippm_conv4x4_bf16_grad_input(const float* gy, const float* w, int
 
 extern "C" int ippm_conv4x4_bf16_grad_weight(const float* gy, const float* x, int64_t batch, int32_t ih, int32_t iw, void* scratch, float* gw,
                                              void* stream) {
-  if (!c4_args_ok("ippm_conv4x4_bf16_grad_weight", gy, x, gw, scratch, batch, ih, iw)) return -1;
+  if (!c4_pass_ok("ippm_conv4x4_bf16_grad_weight", gy, x, gw, scratch, batch, ih, iw)) return -1;
   hipStream_t s = S_(stream);
   const C4Geom g = {ih, iw, ih - 3, iw - 3};
   float* partial = reinterpret_cast<float*>(static_cast<char*>(scratch) + C4_PACKS_BYTES);
-  const int64_t chunks = c4_chunks(batch);
+  const int64_t chunks = lt_ceil_div(batch, IPPM_CONV4X4_WGRAD_CHUNK);
   hipLaunchKernelGGL(k_conv4x4_wgrad, dim3((unsigned)(chunks * 64)), dim3(256), 0, s, gy, x, partial, batch, g);
-  hipLaunchKernelGGL(k_conv4x4_wgrad_sum, dim3((unsigned)(C4_W / 256)), dim3(256), 0, s, partial, chunks, gw);
+  hipLaunchKernelGGL(k_partial_sum<C4SumMap>, dim3((unsigned)(C4_W / 256)), dim3(256), 0, s, partial, chunks, gw);
   IPPM_LAUNCH_CHECK("conv4x4_bf16_grad_weight");
   return 0;
 }

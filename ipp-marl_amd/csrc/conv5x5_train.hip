@@ -9,18 +9,17 @@
 // for inference; the 5 taps of a kernel row and their channels are 5 * PLANES contiguous floats of the input and the next kernel row
 // starts 11 * PLANES floats further on, so no im2col buffer exists.  The padded k are ZERO in LDS and are never read from memory.
 //
-// Forward: the implicit GEMM of k_actor_layer<true, PLANES> (ippm_bf16_net.h: 128 rows x 128 channels, lt_mma_step) with a float32 store.
+// Forward: the implicit GEMM of k_actor_layer<true, PLANES> (ippm_bf16_net.h, on the tile of ippm_bf16_tile.h) with a float32 store.
 // Weight gradient: gw[o][k] = sum over r = (b,oy,ox) of gy[r][o] * x[r + offset(k)].  The output is tiny (256 x K) and gy is the big
 // operand (1 KiB per row), so a workgroup owns (chunk of IPPM_CONV5X5_WGRAD_CHUNK samples, 64 output channels, ALL of K): gy is read once,
 // the small input four times.  Both tiles go into LDS transposed ([o][r], [k][r]); a wavefront owns 64 o x K/4 k.  The float32 partial
-// sums of a chunk go to the scratch [chunk][k][o]; k_conv5x5_wgrad_sum adds them in chunk order and writes PyTorch's [256,PLANES,5,5].
+// sums of a chunk go to the scratch [chunk][k][o]; k_partial_sum<C5SumMap> adds them in chunk order and writes PyTorch's [256,PLANES,5,5].
 #include "ippm_bf16_net.h"
 
 namespace {
 
 constexpr int C5_OUT = 256;                                 // output channels
 constexpr int C5_OP = 49, C5_IP = 121;                      // output / input positions per sample
-constexpr int64_t C5_MAX_BATCH = (int64_t)1 << 24;          // keeps every grid below 2^31 workgroups
 constexpr int C5_WG_O = 64;                                 // output channels per workgroup of the weight gradient
 
 template <int PLANES>
@@ -30,14 +29,6 @@ struct C5 {
   static constexpr int64_t PACK_BYTES = (int64_t)C5_OUT * K * 2;       // bf16 [o][k] (a multiple of 16)
   static constexpr int64_t PARTIAL = (int64_t)C5_OUT * K;             // floats of one chunk's partial sums [k][o]
 };
-
-// two floats -> two bf16 in one word (the first in the low half), round to nearest even: gfx950's packed conversion, one instruction
-// where ai_bf16 is six -- the staging of these kernels converts far more elements per MFMA than the 256-channel layers do
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t c5_bf16x2(float lo, float hi) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(floatx2{lo, hi}, bf16x2));
-}
 
 // offset, within a sample, of element k of an output position's patch relative to the position's first input element
 template <int PLANES>
@@ -60,6 +51,8 @@ __global__ void __launch_bounds__(256) k_conv5x5_pack(const float* __restrict__ 
 // ---- forward --------------------------------------------------------------------------------------------------------------------------
 // y[m][n] = sum_k x[patch(m)][k] * W[n][k], m = (sample, oy, ox) of M rows; bias non-null: y = relu(y + bias[n]) with the arithmetic of
 // k_bias_relu (learn.hip), NaN let through (ippm_relu).
+// The K loop and the store are written out here: on lt_k_loop and lt_for_outputs the 7-plane forward measured 1.2 % slower
+// (profiles/r20/README.md); the instruction stream of this form is the one measured before the tile header existed.
 template <int PLANES>
 __global__ void __launch_bounds__(256)
 k_conv5x5(const float* __restrict__ in, const uint16_t* __restrict__ w, const float* __restrict__ bias, float* __restrict__ out, int64_t M) {
@@ -105,7 +98,7 @@ k_conv5x5(const float* __restrict__ in, const uint16_t* __restrict__ w, const fl
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[i][j] = (a_ok[i] && k + j < G::K_REAL) ? v[i][j] : 0.f;
-      a_reg[i] = u32x4{c5_bf16x2(v[i][0], v[i][1]), c5_bf16x2(v[i][2], v[i][3]), c5_bf16x2(v[i][4], v[i][5]), c5_bf16x2(v[i][6], v[i][7])};
+      a_reg[i] = lt_cvt8(v[i]);
     }
   };
   auto stage = [&]() __attribute__((always_inline)) {
@@ -117,10 +110,7 @@ k_conv5x5(const float* __restrict__ in, const uint16_t* __restrict__ w, const fl
   };
 
   floatx4 acc[4][4];   // [n tile][m tile]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
+  lt_zero(acc);
 
   const int fr = lane & 15, fk = (lane >> 4) * 8;
   load(0);
@@ -183,7 +173,8 @@ k_conv5x5_wgrad(const float* __restrict__ gy, const float* __restrict__ x, float
   u32x4 xr[NI];
   float4 gr[4];
   int g_ok = 0;                                             // how many of gr's rows exist
-  auto load = [&](int k0) __attribute__((always_inline)) {
+  auto load = [&](int s) __attribute__((always_inline)) {
+    const int k0 = s * LT_K;
     {
       const int r0 = k0 + grq * 4;      // (a row past the chunk reads the chunk's first row and is zeroed at the rounding)
 #pragma unroll
@@ -215,7 +206,7 @@ k_conv5x5_wgrad(const float* __restrict__ gy, const float* __restrict__ x, float
       for (int i = 0; i < NI; ++i) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[i][j] = (koff[i] >= 0 && ok[j]) ? v[i][j] : 0.f;
-        xr[i] = u32x4{c5_bf16x2(v[i][0], v[i][1]), c5_bf16x2(v[i][2], v[i][3]), c5_bf16x2(v[i][4], v[i][5]), c5_bf16x2(v[i][6], v[i][7])};
+        xr[i] = lt_cvt8(v[i]);
       }
     }
   };
@@ -228,25 +219,15 @@ k_conv5x5_wgrad(const float* __restrict__ gy, const float* __restrict__ x, float
       float h[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) h[j] = j < g_ok ? gf[j * 4 + q] : 0.f;
-      *reinterpret_cast<uint2*>(&Gs[(gc + q) * LT_LD + grq * 4]) = make_uint2(c5_bf16x2(h[0], h[1]), c5_bf16x2(h[2], h[3]));
+      *reinterpret_cast<uint2*>(&Gs[(gc + q) * LT_LD + grq * 4]) = make_uint2(lt_cvt2(h[0], h[1]), lt_cvt2(h[2], h[3]));
     }
   };
 
   floatx4 acc[4][NT];   // [o tile][k tile]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < NT; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-
+  lt_zero(acc);
   const int fr = lane & 15, fk = (lane >> 4) * 8;
   const int wk = wave * (NT * 16);                          // first k of this wavefront
-  load(0);
-#pragma unroll 1
-  for (int k0 = 0; k0 < R; k0 += LT_K) {
-    __syncthreads();
-    stage();
-    __syncthreads();
-    if (k0 + LT_K < R) load(k0 + LT_K);
+  lt_k_loop<LT_GUARDED, LT_ROLLED>((R + LT_K - 1) / LT_K, load, stage, [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int kk = 0; kk < LT_K; kk += 32) {
       bf16x8 gf[4], xf[NT];
@@ -259,53 +240,39 @@ k_conv5x5_wgrad(const float* __restrict__ gy, const float* __restrict__ x, float
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt) acc[ot][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf[ot], xf[kt], acc[ot][kt], 0, 0, 0);
     }
-  }
+  });
 
-  // D[o][k]: lane holds k = lane & 15 and o = (lane >> 4) * 4 + reg; partial [chunk][k][o]
+  // m is k, n is o; partial [chunk][k][o]
   float* pt = partial + chunk * G::PARTIAL;
-#pragma unroll
-  for (int kt = 0; kt < NT; ++kt) {
-    const int k = wk + kt * 16 + fr;
-#pragma unroll
-    for (int ot = 0; ot < 4; ++ot) {
-      const int o = o0 + ot * 16 + (lane >> 4) * 4;
-      *reinterpret_cast<float4*>(pt + k * C5_OUT + o) = float4{acc[ot][kt][0], acc[ot][kt][1], acc[ot][kt][2], acc[ot][kt][3]};
-    }
-  }
+  auto row = [&](int kl) __attribute__((always_inline)) { return pt + (wk + kl) * C5_OUT; };
+  lt_for_outputs(acc, row, [&](float* prow, int ol, const float4& v) __attribute__((always_inline)) {
+    *reinterpret_cast<float4*>(prow + (o0 + ol)) = v;
+  });
 }
 
-// gw[o][c][tap] = the partials [chunk][k][o] added in chunk order; one thread per element of the real k, reads coalesced over o
+// gw[o][c][tap] from element i = (k, o) of the partials [chunk][k][o], the real k only: the reads are coalesced over o
 template <int PLANES>
-__global__ void __launch_bounds__(256)
-k_conv5x5_wgrad_sum(const float* __restrict__ partial, int64_t chunks, float* __restrict__ gw) {
-  using G = C5<PLANES>;
-  const int i = blockIdx.x * 256 + threadIdx.x;             // < K_REAL * 256: (k, o)
-  float s = 0.f;
-  for (int64_t ch = 0; ch < chunks; ++ch) s += partial[ch * G::PARTIAL + i];
-  const int o = i & 255, k = i >> 8, tap = k / PLANES, c = k - tap * PLANES;
-  gw[(o * PLANES + c) * 25 + tap] = s;
-}
+struct C5SumMap {
+  static constexpr int64_t STRIDE = C5<PLANES>::PARTIAL;
+  static __device__ int out(int i) {
+    const int o = i & 255, k = i >> 8, tap = k / PLANES, c = k - tap * PLANES;
+    return (o * PLANES + c) * 25 + tap;
+  }
+};
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
 bool c5_shape_ok(const char* who, int64_t batch, int32_t planes) {
-  if (batch < 1 || batch > C5_MAX_BATCH) { ippm_set_error(std::string(who) + ": batch must be in [1, 2^24]"); return false; }
+  if (!lt_batch_ok(who, batch)) return false;
   if (planes != 7 && planes != 12) { ippm_set_error(std::string(who) + ": planes must be 7 or 12"); return false; }
   return true;
 }
 
-// (bias, the only optional pointer, is checked by the forward itself)
-bool c5_args_ok(const char* who, const void* a, const void* b, const void* out, const void* scratch, int64_t batch, int32_t planes) {
-  if (!a || !b || !out || !scratch) { ippm_set_error(std::string(who) + ": null argument"); return false; }
-  if (!c5_shape_ok(who, batch, planes)) return false;
-  if (reinterpret_cast<uintptr_t>(scratch) & 15) { ippm_set_error(std::string(who) + ": scratch must be 16-byte aligned"); return false; }
-  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) & 15) {
-    ippm_set_error(std::string(who) + ": the tensors must be 16-byte aligned");
-    return false;
-  }
-  return true;
+// the two passes: two tensors in, one out, the scratch; optional: bias, the one pointer that may be null
+bool c5_pass_ok(const char* who, const void* a, const void* b, const void* out, const void* scratch, const void* optional, int64_t batch,
+                int32_t planes) {
+  return lt_args_ok(who, {a, b, out, scratch}, [&] { return c5_shape_ok(who, batch, planes); }, {scratch}, "scratch") &&
+         lt_aligned_ok(who, {a, b, out, optional}, "the tensors");
 }
-
-int64_t c5_chunks(int64_t batch) { return (batch + IPPM_CONV5X5_WGRAD_CHUNK - 1) / IPPM_CONV5X5_WGRAD_CHUNK; }
 
 template <int PLANES>
 void c5_forward(const float* x, const float* w, const float* bias, int64_t batch, void* scratch, float* y, hipStream_t s) {
@@ -320,9 +287,9 @@ template <int PLANES>
 void c5_grad_weight(const float* gy, const float* x, int64_t batch, void* scratch, float* gw, hipStream_t s) {
   using G = C5<PLANES>;
   float* partial = reinterpret_cast<float*>(static_cast<char*>(scratch) + G::PACK_BYTES);
-  const int64_t chunks = c5_chunks(batch);
+  const int64_t chunks = lt_ceil_div(batch, IPPM_CONV5X5_WGRAD_CHUNK);
   hipLaunchKernelGGL(k_conv5x5_wgrad<PLANES>, dim3((unsigned)(chunks * (C5_OUT / C5_WG_O))), dim3(256), 0, s, gy, x, partial, batch);
-  hipLaunchKernelGGL(k_conv5x5_wgrad_sum<PLANES>, dim3(G::K_REAL), dim3(256), 0, s, partial, chunks, gw);
+  hipLaunchKernelGGL(k_partial_sum<C5SumMap<PLANES>>, dim3(G::K_REAL), dim3(256), 0, s, partial, chunks, gw);
 }
 
 }  // namespace
@@ -330,14 +297,14 @@ void c5_grad_weight(const float* gy, const float* x, int64_t batch, void* scratc
 extern "C" int ippm_conv5x5_bf16_scratch_bytes(int64_t batch, int32_t planes, int64_t* bytes) {
   if (!bytes) { ippm_set_error("ippm_conv5x5_bf16_scratch_bytes: null argument"); return -1; }
   if (!c5_shape_ok("ippm_conv5x5_bf16_scratch_bytes", batch, planes)) return -1;
-  *bytes = planes == 7 ? C5<7>::PACK_BYTES + c5_chunks(batch) * C5<7>::PARTIAL * 4 : C5<12>::PACK_BYTES + c5_chunks(batch) * C5<12>::PARTIAL * 4;
+  const int64_t chunks = lt_ceil_div(batch, IPPM_CONV5X5_WGRAD_CHUNK);
+  *bytes = planes == 7 ? C5<7>::PACK_BYTES + chunks * C5<7>::PARTIAL * 4 : C5<12>::PACK_BYTES + chunks * C5<12>::PARTIAL * 4;
   return 0;
 }
 
 extern "C" int ippm_conv5x5_bf16_forward(const float* x, const float* w, const float* bias, int64_t batch, int32_t planes, void* scratch,
                                          float* y, void* stream) {
-  if (!c5_args_ok("ippm_conv5x5_bf16_forward", x, w, y, scratch, batch, planes)) return -1;
-  if (reinterpret_cast<uintptr_t>(bias) & 15) { ippm_set_error("ippm_conv5x5_bf16_forward: the tensors must be 16-byte aligned"); return -1; }
+  if (!c5_pass_ok("ippm_conv5x5_bf16_forward", x, w, y, scratch, bias, batch, planes)) return -1;
   if (planes == 7) c5_forward<7>(x, w, bias, batch, scratch, y, S_(stream));
   else c5_forward<12>(x, w, bias, batch, scratch, y, S_(stream));
   IPPM_LAUNCH_CHECK("conv5x5_bf16_forward");
@@ -346,7 +313,7 @@ extern "C" int ippm_conv5x5_bf16_forward(const float* x, const float* w, const f
 
 extern "C" int ippm_conv5x5_bf16_grad_weight(const float* gy, const float* x, int64_t batch, int32_t planes, void* scratch, float* gw,
                                              void* stream) {
-  if (!c5_args_ok("ippm_conv5x5_bf16_grad_weight", gy, x, gw, scratch, batch, planes)) return -1;
+  if (!c5_pass_ok("ippm_conv5x5_bf16_grad_weight", gy, x, gw, scratch, nullptr, batch, planes)) return -1;
   if (planes == 7) c5_grad_weight<7>(gy, x, batch, scratch, gw, S_(stream));
   else c5_grad_weight<12>(gy, x, batch, scratch, gw, S_(stream));
   IPPM_LAUNCH_CHECK("conv5x5_bf16_grad_weight");

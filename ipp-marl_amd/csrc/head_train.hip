@@ -9,14 +9,12 @@
 // No float atomics; every output element has one owner and a fixed summation order.  Sums over the batch (gW1, gb1, gW3, gb3, the loss)
 // are per-chunk partial sums (IPPM_HEAD_WGRAD_CHUNK samples) in the scratch, added in chunk order by a second kernel.
 //
-// Row kernels (k_head_rows, k_head_gz1) own HT_M = 64 rows and all 256 columns: one workgroup, four wavefronts of 64 x 64 (lt_mma_step).
+// Row kernels (k_head_rows, k_head_gz1) own HT_M = 64 rows and all 256 columns: one workgroup, four wavefronts of 64 x 64 (the tile of ippm_bf16_tile.h).
 // The weights arrive as float32 and are rounded while they are staged -- no pack kernel: these passes are launch-bound at the reference's
 // 60-sample minibatch, where the staging of the 256 KiB of fc1's weight IS the kernel's duration whatever the row tile, and a tile of 64
 // rows is the smallest that does not multiply that staging at the large batches.
 // Every load is unconditional on a clamped address (a row, a column or an action that does not exist reads the tensor's first and is
 // zeroed afterwards).
-#include <initializer_list>
-
 #include "ippm_bf16_net.h"
 
 namespace {
@@ -25,31 +23,26 @@ constexpr int HD = AI_N;                                    // width of h, a1 an
 constexpr int HT_M = 64;                                    // rows per workgroup of the row kernels
 constexpr int HC = IPPM_HEAD_WGRAD_CHUNK;                   // samples per partial sum
 static_assert(HC == LT_K && HC == HT_M, "a chunk is one K step of the weight-gradient GEMM and one row tile");
-constexpr int64_t HD_MAX_BATCH = (int64_t)1 << 24;          // keeps every grid below 2^31 workgroups
 constexpr int A1_LD = HD + 8;                               // LDS row of the bf16 a1 tile
 constexpr int D_LD = AI_NPAD + 8;                           // LDS row of the (action-padded) tiles of k_head_gz1
 // floats of one chunk's partial sums: gW1 [k][o], gW3 [k][a padded], gb1, gb3
 constexpr int64_t HP_W1 = 0, HP_W3 = HP_W1 + (int64_t)HD * HD, HP_B1 = HP_W3 + (int64_t)HD * AI_NPAD, HP_B3 = HP_B1 + HD;
 constexpr int64_t HP_FLOATS = HP_B3 + AI_NPAD;
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t hd_bf16x2(float lo, float hi) {   // two floats -> two bf16 in a word, nearest even (one instruction)
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(floatx2{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ u32x4 hd_bf16x8(const float (&v)[8]) {
-  return u32x4{hd_bf16x2(v[0], v[1]), hd_bf16x2(v[2], v[3]), hd_bf16x2(v[4], v[5]), hd_bf16x2(v[6], v[7])};
-}
-
-int64_t hd_chunks(int64_t batch) { return (batch + HC - 1) / HC; }
+// lt_for_tiles' answer about a row of these kernels: none is skipped (rows past the batch still go into the a1 tile in LDS)
+struct HdRow {
+  int ml;
+  __device__ explicit operator bool() const { return true; }
+};
+__device__ __forceinline__ HdRow hd_every_row(int ml) { return HdRow{ml}; }
 
 // the scratch: the loss's partial sums double [chunks] (padded to 16 bytes), gz1 [B,256], the weight gradients' partial sums
 // [chunks][HP_FLOATS]
 struct HeadScratch {
   double* loss;
   float *gz1, *partial;
-  static int64_t loss_doubles(int64_t batch) { return (hd_chunks(batch) + 1) / 2 * 2; }
-  static int64_t bytes(int64_t batch) { return loss_doubles(batch) * 8 + (batch * HD + hd_chunks(batch) * HP_FLOATS) * 4; }
+  static int64_t loss_doubles(int64_t batch) { return (lt_ceil_div(batch, HC) + 1) / 2 * 2; }
+  static int64_t bytes(int64_t batch) { return loss_doubles(batch) * 8 + (batch * HD + lt_ceil_div(batch, HC) * HP_FLOATS) * 4; }
   HeadScratch(void* scratch, int64_t batch) {
     loss = static_cast<double*>(scratch);
     gz1 = reinterpret_cast<float*>(loss + loss_doubles(batch));
@@ -70,10 +63,11 @@ k_head_rows(const float* __restrict__ x, const float* __restrict__ w1, const flo
   static_assert(HT_M * A1_LD <= HD * LT_LD, "the a1 tile fits into the weight tile");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t m0 = (int64_t)blockIdx.x * HT_M;
-  const int sc = tid & 7, sr = tid >> 3;                                     // staging: 8 k from sc * 8 on, rows sr + 32 i
+  const int sc = tid & 7, sr = tid >> 3;
 
   u32x4 a_reg[2], w_reg[8];
-  auto load = [&](int k0) __attribute__((always_inline)) {
+  auto load = [&](int s) __attribute__((always_inline)) {
+    const int k0 = s * LT_K;
     float4 xv[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -91,7 +85,7 @@ k_head_rows(const float* __restrict__ x, const float* __restrict__ w1, const flo
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float v[8] = {wv[i][0].x, wv[i][0].y, wv[i][0].z, wv[i][0].w, wv[i][1].x, wv[i][1].y, wv[i][1].z, wv[i][1].w};
-        w_reg[i] = hd_bf16x8(v);
+        w_reg[i] = lt_cvt8(v);
       }
     } else {
       // Ws[n = tid][k - k0]: 8 consecutive k of one n are 8 rows of W1; lanes next to each other read floats next to each other
@@ -101,7 +95,7 @@ k_head_rows(const float* __restrict__ x, const float* __restrict__ w1, const flo
 #pragma unroll
         for (int j = 0; j < 8; ++j) wv[g][j] = w1[(k0 + g * 8 + j) * HD + tid];
 #pragma unroll
-      for (int g = 0; g < 8; ++g) w_reg[g] = hd_bf16x8(wv[g]);
+      for (int g = 0; g < 8; ++g) w_reg[g] = lt_cvt8(wv[g]);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -109,62 +103,43 @@ k_head_rows(const float* __restrict__ x, const float* __restrict__ w1, const flo
       float v[8] = {xv[i][0].x, xv[i][0].y, xv[i][0].z, xv[i][0].w, xv[i][1].x, xv[i][1].y, xv[i][1].z, xv[i][1].w};
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = ok ? v[j] : 0.f;
-      a_reg[i] = hd_bf16x8(v);
+      a_reg[i] = lt_cvt8(v);
     }
   };
   auto stage = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) *reinterpret_cast<u32x4*>(&As[(sr + 32 * i) * LT_LD + sc * 8]) = a_reg[i];
+    for (int i = 0; i < 2; ++i) lt_stage_row(As, i, a_reg[i]);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      if (FORWARD) *reinterpret_cast<u32x4*>(&Ws[(sr + 32 * i) * LT_LD + sc * 8]) = w_reg[i];
+      if (FORWARD) lt_stage_row(Ws, i, w_reg[i]);
       else *reinterpret_cast<u32x4*>(&Ws[tid * LT_LD + i * 8]) = w_reg[i];
     }
   };
 
   floatx4 acc[4][4];   // [n tile][m tile]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  const int fr = lane & 15, fk = (lane >> 4) * 8;
+  lt_zero(acc);
   const int wn = wave * 64;
-  load(0);
-#pragma unroll 1
-  for (int k0 = 0; k0 < HD; k0 += LT_K) {
-    __syncthreads();          // the previous step's fragment reads are done
-    stage();
-    __syncthreads();
-    if (k0 + LT_K < HD) load(k0 + LT_K);   // (uniform over the workgroup)
-    lt_mma_step(As, Ws, 0, wn, fr, fk, acc);
-  }
+  lt_k_loop<LT_GUARDED, LT_ROLLED>(HD / LT_K, load, stage, As, Ws, 0, wn, acc);
 
-  // D[n][m]: lane holds m = lane & 15 and n = (lane >> 4) * 4 + reg
   uint16_t* A1s = Ws;
   if (FORWARD) __syncthreads();            // every wavefront is done with the weight tile
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int ml = mt * 16 + fr;
+  lt_for_outputs(acc, hd_every_row, [&](HdRow r, int nl, float4 v) __attribute__((always_inline)) {
+    const int ml = r.ml;
     const int64_t m = m0 + ml;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const int n = wn + nt * 16 + (lane >> 4) * 4;
-      float4 v = float4{acc[nt][mt][0], acc[nt][mt][1], acc[nt][mt][2], acc[nt][mt][3]};
-      if (FORWARD) {
-        const float4 bv = *reinterpret_cast<const float4*>(b1 + n);
-        v.x = ippm_relu(v.x + bv.x); v.y = ippm_relu(v.y + bv.y); v.z = ippm_relu(v.z + bv.z); v.w = ippm_relu(v.w + bv.w);
-        *reinterpret_cast<uint2*>(&A1s[ml * A1_LD + n]) = make_uint2(hd_bf16x2(v.x, v.y), hd_bf16x2(v.z, v.w));
-      }
-      if (m < B) *reinterpret_cast<float4*>(out + m * HD + n) = v;
+    const int n = wn + nl;
+    if (FORWARD) {
+      const float4 bv = *reinterpret_cast<const float4*>(b1 + n);
+      v.x = ippm_relu(v.x + bv.x); v.y = ippm_relu(v.y + bv.y); v.z = ippm_relu(v.z + bv.z); v.w = ippm_relu(v.w + bv.w);
+      *reinterpret_cast<uint2*>(&A1s[ml * A1_LD + n]) = make_uint2(lt_cvt2(v.x, v.y), lt_cvt2(v.z, v.w));
     }
-  }
+    if (m < B) *reinterpret_cast<float4*>(out + m * HD + n) = v;
+  });
   if (!FORWARD) return;
   __syncthreads();
 
   // fc3: this wavefront's 16 rows x the 32 padded actions
-  floatx4 acc3[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
-  const int ml = wave * 16 + fr;
+  floatx4 acc3[2] = {};
+  const int fr = lane & 15, fk = (lane >> 4) * 8, ml = wave * 16 + fr;
 #pragma unroll
   for (int k = 0; k < HD; k += 32) {
     const bf16x8 af = *reinterpret_cast<const bf16x8*>(&A1s[ml * A1_LD + k + fk]);
@@ -176,7 +151,7 @@ k_head_rows(const float* __restrict__ x, const float* __restrict__ w1, const flo
       float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = a < A ? v[j] : 0.f;
-      acc3[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, hd_bf16x8(v)), af, acc3[nt], 0, 0, 0);
+      acc3[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, lt_cvt8(v)), af, acc3[nt], 0, 0, 0);
     }
   }
   const int64_t m = m0 + ml;
@@ -208,7 +183,7 @@ k_head_gz1(const float* __restrict__ dlogits, const float* __restrict__ scale_de
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float q[8] = {v[g * 8], v[g * 8 + 1], v[g * 8 + 2], v[g * 8 + 3], v[g * 8 + 4], v[g * 8 + 5], v[g * 8 + 6], v[g * 8 + 7]};
-      *reinterpret_cast<u32x4*>(&Wt[tid * D_LD + g * 8]) = hd_bf16x8(q);
+      *reinterpret_cast<u32x4*>(&Wt[tid * D_LD + g * 8]) = lt_cvt8(q);
     }
     const int ml = tid >> 2, a8 = (tid & 3) * 8;
     const int64_t m = m0 + ml;
@@ -217,7 +192,7 @@ k_head_gz1(const float* __restrict__ dlogits, const float* __restrict__ scale_de
     for (int j = 0; j < 8; ++j) d[j] = dlogits[(m < B ? m : 0) * A + (a8 + j < A ? a8 + j : 0)];
 #pragma unroll
     for (int j = 0; j < 8; ++j) d[j] = (m < B && a8 + j < A) ? d[j] * scale : 0.f;
-    *reinterpret_cast<u32x4*>(&Ds[ml * D_LD + a8]) = hd_bf16x8(d);
+    *reinterpret_cast<u32x4*>(&Ds[ml * D_LD + a8]) = lt_cvt8(d);
   }
   __syncthreads();
   const int fr = lane & 15, fk = (lane >> 4) * 8, wn = wave * 64;
@@ -227,21 +202,18 @@ k_head_gz1(const float* __restrict__ dlogits, const float* __restrict__ scale_de
     af[t] = *reinterpret_cast<const bf16x8*>(&Ds[(t * 16 + fr) * D_LD + fk]);
     wf[t] = *reinterpret_cast<const bf16x8*>(&Wt[(wn + t * 16 + fr) * D_LD + fk]);
   }
-  // D[n][m]: lane holds m = lane & 15 and n = (lane >> 4) * 4 + reg
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int64_t m = m0 + mt * 16 + fr;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const int n = wn + nt * 16 + (lane >> 4) * 4;
-      const floatx4 g = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt], af[mt], floatx4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      const float4 a = *reinterpret_cast<const float4*>(a1 + (m < B ? m : 0) * HD + n);
-      // the mask is a FACTOR, as the definition has it (gz1 = ga1 [a1 > 0]): a non-finite ga1 behind a closed ReLU gives NaN, not 0
-      const float4 o = float4{g[0] * (a.x > 0.f ? 1.f : 0.f), g[1] * (a.y > 0.f ? 1.f : 0.f), g[2] * (a.z > 0.f ? 1.f : 0.f),
-                              g[3] * (a.w > 0.f ? 1.f : 0.f)};
-      if (m < B) *reinterpret_cast<float4*>(gz1 + m * HD + n) = o;
-    }
-  }
+  auto tile = [&](int nt, int mt) __attribute__((always_inline)) {   // K is one MFMA: a tile is made when its outputs are asked for
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt], af[mt], floatx4{}, 0, 0, 0);
+  };
+  lt_for_tiles<4>(tile, hd_every_row, [&](HdRow r, int nl, const float4& g) __attribute__((always_inline)) {
+    const int64_t m = m0 + r.ml;
+    const int n = wn + nl;
+    const float4 a = *reinterpret_cast<const float4*>(a1 + (m < B ? m : 0) * HD + n);
+    // the mask is a FACTOR, as the definition has it (gz1 = ga1 [a1 > 0]): a non-finite ga1 behind a closed ReLU gives NaN, not 0
+    const float4 o = float4{g.x * (a.x > 0.f ? 1.f : 0.f), g.y * (a.y > 0.f ? 1.f : 0.f), g.z * (a.z > 0.f ? 1.f : 0.f),
+                            g.w * (a.w > 0.f ? 1.f : 0.f)};
+    if (m < B) *reinterpret_cast<float4*>(gz1 + m * HD + n) = o;
+  });
 }
 
 // ---- the weight and bias gradients of a chunk -----------------------------------------------------------------------------------------
@@ -285,8 +257,8 @@ k_head_wgrad(const float* __restrict__ gz1, const float* __restrict__ dlogits, c
     }
     part[rg][c] = s;
     const float lo[8] = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]}, hi[8] = {v[8], v[9], v[10], v[11], v[12], v[13], v[14], v[15]};
-    *reinterpret_cast<u32x4*>(&Gs[c * LT_LD + rg * 16]) = hd_bf16x8(lo);
-    *reinterpret_cast<u32x4*>(&Gs[c * LT_LD + rg * 16 + 8]) = hd_bf16x8(hi);
+    *reinterpret_cast<u32x4*>(&Gs[c * LT_LD + rg * 16]) = lt_cvt8(lo);
+    *reinterpret_cast<u32x4*>(&Gs[c * LT_LD + rg * 16 + 8]) = lt_cvt8(hi);
   }
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
@@ -301,32 +273,23 @@ k_head_wgrad(const float* __restrict__ gz1, const float* __restrict__ dlogits, c
       float w[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) w[j] = half * 32 + g * 8 + j < ns ? v[g * 8 + j] : 0.f;
-      *reinterpret_cast<u32x4*>(&Xs[tid * LT_LD + half * 32 + g * 8]) = hd_bf16x8(w);
+      *reinterpret_cast<u32x4*>(&Xs[tid * LT_LD + half * 32 + g * 8]) = lt_cvt8(w);
     }
   }
   __syncthreads();
 
   floatx4 acc[4][4];   // [o tile][k tile]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const int fr = lane & 15, fk = (lane >> 4) * 8, wk = wave * 64;
-  lt_mma_step(Xs, Gs, wk, 0, fr, fk, acc);
+  lt_zero(acc);
+  const int wk = wave * 64;
+  lt_mma_step(Xs, Gs, wk, 0, lane & 15, (lane >> 4) * 8, acc);
 
-  // D[o][k]: lane holds k = lane & 15 and o = (lane >> 4) * 4 + reg
+  // m is k, n is o (gW3: the action)
   float* pt = partial + chunk * HP_FLOATS;
-#pragma unroll
-  for (int kt = 0; kt < 4; ++kt) {
-    const int k = wk + kt * 16 + fr;
-#pragma unroll
-    for (int ot = 0; ot < 4; ++ot) {
-      const int o = ot * 16 + (lane >> 4) * 4;
-      const float4 v = float4{acc[ot][kt][0], acc[ot][kt][1], acc[ot][kt][2], acc[ot][kt][3]};
-      if (!third) *reinterpret_cast<float4*>(pt + HP_W1 + k * HD + q * 64 + o) = v;
-      else if (ot < 2) *reinterpret_cast<float4*>(pt + HP_W3 + k * AI_NPAD + o) = v;
-    }
-  }
+  lt_for_outputs(acc, hd_every_row, [&](HdRow r, int o, const float4& v) __attribute__((always_inline)) {
+    const int k = wk + r.ml;
+    if (!third) *reinterpret_cast<float4*>(pt + HP_W1 + k * HD + q * 64 + o) = v;
+    else if (o < AI_NPAD) *reinterpret_cast<float4*>(pt + HP_W3 + k * AI_NPAD + o) = v;
+  });
   if (tid < (third ? AI_NPAD : 64)) {
     const float s = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
     pt[third ? HP_B3 + tid : HP_B1 + q * 64 + tid] = s;
@@ -443,20 +406,11 @@ __global__ void k_head_loss_sum(const double* __restrict__ part, int64_t chunks,
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-bool hd_shape_ok(const char* who, int64_t batch, int32_t n_actions) {
-  if (batch < 1 || batch > HD_MAX_BATCH) { ippm_set_error(std::string(who) + ": batch must be in [1, 2^24]"); return false; }
-  return ai_actions_ok(who, n_actions);
-}
+bool hd_shape_ok(const char* who, int64_t batch, int32_t n_actions) { return lt_batch_ok(who, batch) && ai_actions_ok(who, n_actions); }
 
-// required: may not be null; aligned: must be 16-byte aligned (nulls among them are the optional ones)
 bool hd_args_ok(const char* who, std::initializer_list<const void*> required, std::initializer_list<const void*> aligned, int64_t batch,
                 int32_t n_actions) {
-  for (const void* p : required)
-    if (!p) { ippm_set_error(std::string(who) + ": null argument"); return false; }
-  if (!hd_shape_ok(who, batch, n_actions)) return false;
-  for (const void* p : aligned)
-    if (reinterpret_cast<uintptr_t>(p) & 15) { ippm_set_error(std::string(who) + ": the tensors and the scratch must be 16-byte aligned"); return false; }
-  return true;
+  return lt_args_ok(who, required, [&] { return hd_shape_ok(who, batch, n_actions); }, aligned, "the tensors and the scratch");
 }
 
 unsigned hd_tiles(int64_t batch) { return (unsigned)((batch + HT_M - 1) / HT_M); }
@@ -485,7 +439,7 @@ extern "C" int ippm_critic_loss(const float* q, const int32_t* action, const flo
   const char* who = "ippm_critic_loss";
   if (!hd_args_ok(who, {q, action, td, scratch, loss, q_chosen, dq}, {scratch}, batch, n_actions)) return -1;
   const HeadScratch sc(scratch, batch);
-  const int64_t chunks = hd_chunks(batch);
+  const int64_t chunks = lt_ceil_div(batch, HC);
   hipLaunchKernelGGL(k_critic_loss, dim3((unsigned)chunks), dim3(HC), 0, S_(stream), q, action, td, batch, (int)n_actions, sc.loss, q_chosen, dq);
   hipLaunchKernelGGL(k_head_loss_sum, dim3(1), dim3(64), 0, S_(stream), static_cast<const double*>(sc.loss), chunks, batch, 1.0, loss);
   IPPM_LAUNCH_CHECK("critic_loss");
@@ -498,7 +452,7 @@ extern "C" int ippm_actor_loss(const float* logits, const float* q_values, const
   const char* who = "ippm_actor_loss";
   if (!hd_args_ok(who, {logits, q_values, mask, action, scratch, loss, adv, dlogits}, {scratch}, batch, n_actions)) return -1;
   const HeadScratch sc(scratch, batch);
-  const int64_t chunks = hd_chunks(batch);
+  const int64_t chunks = lt_ceil_div(batch, HC);
   hipLaunchKernelGGL(k_actor_loss, dim3((unsigned)chunks), dim3(256), 0, S_(stream), logits, q_values, mask, action, batch, (int)n_actions, eps,
                      eps_dev, sc.loss, adv, probs, dlogits);
   hipLaunchKernelGGL(k_head_loss_sum, dim3(1), dim3(64), 0, S_(stream), static_cast<const double*>(sc.loss), chunks, batch, -1.0, loss);
@@ -514,7 +468,7 @@ extern "C" int ippm_head_backward(const float* dlogits, const float* scale_dev, 
                   n_actions))
     return -1;
   const HeadScratch sc(scratch, batch);
-  const int64_t chunks = hd_chunks(batch);
+  const int64_t chunks = lt_ceil_div(batch, HC);
   const int A = n_actions;
   hipStream_t s = S_(stream);
   hipLaunchKernelGGL(k_head_gz1, dim3(hd_tiles(batch)), dim3(256), 0, s, dlogits, scale_dev, fc3_w, a1, sc.gz1, batch, A);

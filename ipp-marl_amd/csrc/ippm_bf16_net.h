@@ -13,10 +13,7 @@
 //
 // Everything here sits in an unnamed namespace: each translation unit that includes the header owns its instantiations.
 #pragma once
-#include <cstdint>
-#include <string>
-
-#include "ippm_internal.h"
+#include "ippm_bf16_tile.h"
 
 namespace {
 
@@ -46,28 +43,6 @@ struct NetPack {
 // bf16 activations per sample in the scratch: conv1 [7,7,256], conv2 [4,4,256], conv3 [256], fc1 [256]
 constexpr int64_t AI_ACT1 = 49 * AI_N, AI_ACT2 = 16 * AI_N, AI_ACT3 = AI_N, AI_ACT4 = AI_N;
 constexpr int64_t AI_SCRATCH_PER_SAMPLE = (AI_ACT1 + AI_ACT2 + AI_ACT3 + AI_ACT4) * 2;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint16_t ai_bf16(float x) {   // round to nearest even (NaN kept quiet)
-  uint32_t u = __float_as_uint(x);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-// ai_bf16(ippm_relu(x)) in one pass over the bits: NaN is kept by the test the conversion makes anyway, and what is left of the ReLU --
-// everything with the sign bit set, -0 and -Inf included, becomes +0 -- is one integer max where ippm_relu's two compares and two selects
-// in front of the conversion cost the layer kernel 1.3 % (profiles/r14/)
-__device__ __forceinline__ uint16_t ai_relu_bf16(float x) {
-  uint32_t u = __float_as_uint(x);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u = (uint32_t)max((int32_t)u, 0);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 // ---- packing ---------------------------------------------------------------------------------------------------------------------
 // PyTorch's [O,C,kh,kw] / [O,I] float32 -> [O][K] bf16 with k = (ty*kw + tx)*C + c; one thread per packed element.
@@ -102,10 +77,7 @@ k_net_pack(const float* __restrict__ c1w, const float* __restrict__ c1b, const f
 }
 
 // ---- one hidden layer ------------------------------------------------------------------------------------------------------------
-// Workgroup tile: 128 rows (m) x 128 output channels, 4 wavefronts of 64 x 64 each, K in steps of 64 through LDS (rows padded by 16 bytes:
-// the 16-byte fragment reads of 16 rows then fall into 16 different bank groups).  The next K step's global loads are issued before the
-// MFMAs of the current one.  The weights are the FIRST operand of mfma_f32_16x16x32_bf16, so a lane's 4 accumulator registers are 4
-// consecutive output channels of one row: one 8-byte store.
+// One workgroup tile of ippm_bf16_tile.h per (128 rows, 128 output channels).
 struct LayerGeom {
   int IW, C;       // input width (positions) and channels; an input sample is IH*IW*C elements
   int KW;          // kernel width; K = KH*KW*C
@@ -113,27 +85,6 @@ struct LayerGeom {
   int in_sample;   // elements per input sample
   int K;           // padded K, a multiple of 64
 };
-
-constexpr int LT_M = 128, LT_N = 128, LT_K = 64, LT_LD = LT_K + 8;
-
-// One K step of a wavefront's 64 x 64 share of the tile: acc[n tile][m tile] += Ws[wn ..][k] * As[wm ..][k] over the LT_K k staged in LDS
-// (rows of LT_LD elements; fr = lane & 15, fk = (lane >> 4) * 8).  Shared with the training convolution (conv4x4_train.hip).
-__device__ __forceinline__ void lt_mma_step(const uint16_t* As, const uint16_t* Ws, int wm, int wn, int fr, int fk, floatx4 (&acc)[4][4]) {
-#pragma unroll
-  for (int kk = 0; kk < LT_K; kk += 32) {
-    bf16x8 af[4], wf[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      af[t] = *reinterpret_cast<const bf16x8*>(&As[(wm + t * 16 + fr) * LT_LD + kk + fk]);
-      wf[t] = *reinterpret_cast<const bf16x8*>(&Ws[(wn + t * 16 + fr) * LT_LD + kk + fk]);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-        acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
-  }
-}
 
 // FIRST: the layer reads the float32 network input [B,11,11,PLANES] (5x5 kernel) and rounds it to bf16 on the way into LDS; otherwise
 // the bf16 activation of the layer before (PLANES is not used).
@@ -143,12 +94,11 @@ k_actor_layer(const void* __restrict__ in_, const uint16_t* __restrict__ w, cons
               int64_t M, LayerGeom g) {
   __shared__ __attribute__((aligned(16))) uint16_t As[LT_M * LT_LD];
   __shared__ __attribute__((aligned(16))) uint16_t Ws[LT_N * LT_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, wave = tid >> 6;
   const int64_t m0 = (int64_t)blockIdx.x * LT_M;
   const int n0 = blockIdx.y * LT_N;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
 
-  // staging: thread -> chunk column (8 k) and 4 rows, 32 apart
   const int sc = tid & 7, sr = tid >> 3;
   int64_t a_base[4];
   bool a_ok[4];
@@ -164,8 +114,8 @@ k_actor_layer(const void* __restrict__ in_, const uint16_t* __restrict__ w, cons
   const uint16_t* wrow = w + (int64_t)(n0 + sr) * g.K + sc * 8;
 
   u32x4 a_reg[4], w_reg[4];
-  auto load = [&](int k0) __attribute__((always_inline)) {
-    const int k = k0 + sc * 8;
+  auto load = [&](int s) __attribute__((always_inline)) {
+    const int k0 = s * LT_K, k = k0 + sc * 8;
 #pragma unroll
     for (int i = 0; i < 4; ++i) w_reg[i] = *reinterpret_cast<const u32x4*>(wrow + (int64_t)32 * i * g.K + k0);
     if (FIRST) {
@@ -175,14 +125,13 @@ k_actor_layer(const void* __restrict__ in_, const uint16_t* __restrict__ w, cons
       const float* in = static_cast<const float*>(in_);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        uint32_t h[8];
+        float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int kk = k + j, ty = kk / ROW, r = kk - ty * ROW;
-          const float v = (a_ok[i] && kk < K_REAL) ? in[a_base[i] + ty * STRIDE + r] : 0.f;
-          h[j] = ai_bf16(v);
+          v[j] = (a_ok[i] && kk < K_REAL) ? in[a_base[i] + ty * STRIDE + r] : 0.f;
         }
-        a_reg[i] = u32x4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+        a_reg[i] = lt_round8(v);
       }
     } else {
       const uint16_t* in = static_cast<const uint16_t*>(in_);
@@ -196,42 +145,27 @@ k_actor_layer(const void* __restrict__ in_, const uint16_t* __restrict__ w, cons
   auto stage = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      *reinterpret_cast<u32x4*>(&As[(sr + 32 * i) * LT_LD + sc * 8]) = a_reg[i];
-      *reinterpret_cast<u32x4*>(&Ws[(sr + 32 * i) * LT_LD + sc * 8]) = w_reg[i];
+      lt_stage_row(As, i, a_reg[i]);
+      lt_stage_row(Ws, i, w_reg[i]);
     }
   };
 
   floatx4 acc[4][4];   // [n tile][m tile]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
+  lt_zero(acc);
+  lt_k_loop<LT_RELOAD_LAST, LT_FREE>(g.K / LT_K, load, stage, As, Ws, wm, wn, acc);
 
-  const int fr = lane & 15, fk = (lane >> 4) * 8;
-  load(0);
-  for (int k0 = 0; k0 < g.K; k0 += LT_K) {
-    __syncthreads();          // the previous step's fragment reads are done
-    stage();
-    __syncthreads();
-    load(k0 + LT_K < g.K ? k0 + LT_K : k0);   // (the last step re-reads its own tile: no branch around the loads)
-    lt_mma_step(As, Ws, wm, wn, fr, fk, acc);
-  }
-
-  // D[n][m]: lane holds m = lane & 15 and n = (lane >> 4) * 4 + reg
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int64_t m = m0 + wm + mt * 16 + fr;
-    if (m >= M) continue;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const int n = n0 + wn + nt * 16 + (lane >> 4) * 4;
-      const float4 bv = *reinterpret_cast<const float4*>(bias + n);
-      uint2 o;   // the NaN-passing ReLU of every bf16 store (ippm_relu), then the rounding
-      o.x = (uint32_t)ai_relu_bf16(acc[nt][mt][0] + bv.x) | ((uint32_t)ai_relu_bf16(acc[nt][mt][1] + bv.y) << 16);
-      o.y = (uint32_t)ai_relu_bf16(acc[nt][mt][2] + bv.z) | ((uint32_t)ai_relu_bf16(acc[nt][mt][3] + bv.w) << 16);
-      *reinterpret_cast<uint2*>(out + m * AI_N + n) = o;
-    }
-  }
+  auto row = [&](int ml) __attribute__((always_inline)) {
+    const int64_t m = m0 + wm + ml;
+    return m < M ? out + m * AI_N : nullptr;
+  };
+  lt_for_outputs(acc, row, [&](uint16_t* orow, int nl, const float4& v) __attribute__((always_inline)) {
+    const int n = n0 + wn + nl;
+    const float4 bv = *reinterpret_cast<const float4*>(bias + n);
+    uint2 o;   // the NaN-passing ReLU of every bf16 store (ippm_relu), then the rounding
+    o.x = (uint32_t)ai_relu_bf16(v.x + bv.x) | ((uint32_t)ai_relu_bf16(v.y + bv.y) << 16);
+    o.y = (uint32_t)ai_relu_bf16(v.z + bv.z) | ((uint32_t)ai_relu_bf16(v.w + bv.w) << 16);
+    *reinterpret_cast<uint2*>(orow + n) = o;
+  });
 }
 
 // ---- fc3 on the matrix cores: one wavefront per 16 samples -------------------------------------------------------------------------
@@ -241,7 +175,7 @@ __device__ __forceinline__ void ai_fc3_tile(const uint16_t* __restrict__ h, cons
                                             int64_t b0, int64_t B, float (*L)[AI_NPAD + 1]) {
   const int lane = threadIdx.x, fr = lane & 15, fk = (lane >> 4) * 8;
   const int64_t m = b0 + fr;
-  floatx4 acc[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
+  floatx4 acc[2] = {};
 #pragma unroll
   for (int k = 0; k < AI_K4; k += 32) {
     uint4 a = make_uint4(0, 0, 0, 0);

@@ -187,6 +187,14 @@ class _ConvDataGradAsGemm(torch.autograd.Function):
         return grad_x, grad_w, grad_b
 
 
+def _scratch(bytes_entry: str, args: tuple, device) -> torch.Tensor:
+    """The scratch tensor of a bf16 entry point family: the library's ``bytes_entry(*args, &bytes)`` is asked for the size."""
+    from . import _ffi
+    nbytes = ctypes.c_int64(0)
+    _ffi.check(getattr(_ffi.load_library(), bytes_entry)(*args, ctypes.addressof(nbytes)), bytes_entry)
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
 class _Conv4x4Bf16(torch.autograd.Function):
     """Bias-free conv2 (4x4, 256 -> 256 channels, stride 1, no padding) whose forward, input gradient and weight gradient run on the
     bf16 matrix cores (libippmarl's ippm_conv4x4_bf16_*, csrc/conv4x4_train.hip) instead of the library's float32 convolution.
@@ -205,10 +213,8 @@ class _Conv4x4Bf16(torch.autograd.Function):
     def _call(name: str, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, batch: int, ih: int, iw: int, partials: bool):
         from . import _ffi
         lib = _ffi.load_library()
-        nbytes = ctypes.c_int64(0)
         # (forward and input gradient use the weight packs at the head of the scratch only: the size of a one-sample call)
-        _ffi.check(lib.ippm_conv4x4_bf16_scratch_bytes(batch if partials else 1, ih, iw, ctypes.addressof(nbytes)), "ippm_conv4x4_bf16_scratch_bytes")
-        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=out.device)
+        scratch = _scratch("ippm_conv4x4_bf16_scratch_bytes", (batch if partials else 1, ih, iw), out.device)
         _ffi.check(getattr(lib, name)(a.data_ptr(), b.data_ptr(), batch, ih, iw, scratch.data_ptr(), out.data_ptr(),
                                       torch.cuda.current_stream(out.device).cuda_stream), name)
         return out
@@ -285,13 +291,6 @@ class _Conv5x5Bf16(torch.autograd.Function):
                 and not x.requires_grad and x.is_contiguous(memory_format=torch.channels_last))
 
     @staticmethod
-    def _scratch(lib, batch: int, planes: int, device):
-        from . import _ffi
-        nbytes = ctypes.c_int64(0)
-        _ffi.check(lib.ippm_conv5x5_bf16_scratch_bytes(batch, planes, ctypes.addressof(nbytes)), "ippm_conv5x5_bf16_scratch_bytes")
-        return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-
-    @staticmethod
     def forward(ctx, x, weight, bias):
         from . import _ffi
         lib = _ffi.load_library()
@@ -301,7 +300,7 @@ class _Conv5x5Bf16(torch.autograd.Function):
         B, planes = xs.shape[0], xs.shape[1]
         y = torch.empty((B, 256, 7, 7), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         # (the forward uses the weight pack at the head of the scratch only: the size of a one-sample call minus its partial sums)
-        scratch = _Conv5x5Bf16._scratch(lib, 1, planes, x.device)
+        scratch = _scratch("ippm_conv5x5_bf16_scratch_bytes", (1, planes), x.device)
         _ffi.check(lib.ippm_conv5x5_bf16_forward(xs.data_ptr(), w.data_ptr(), b.data_ptr(), B, planes, scratch.data_ptr(), y.data_ptr(),
                                                  torch.cuda.current_stream(x.device).cuda_stream), "ippm_conv5x5_bf16_forward")
         ctx.save_for_backward(xs, y)
@@ -329,21 +328,17 @@ class _Conv5x5Bf16(torch.autograd.Function):
         lib = _ffi.load_library()
         B, planes = xs.shape[0], xs.shape[1]
         grad_w = torch.empty((256, planes, 5, 5), dtype=xs.dtype, device=xs.device)
-        scratch = _Conv5x5Bf16._scratch(lib, B, planes, xs.device)
+        scratch = _scratch("ippm_conv5x5_bf16_scratch_bytes", (B, planes), xs.device)
         _ffi.check(lib.ippm_conv5x5_bf16_grad_weight(grad_pre.data_ptr(), xs.data_ptr(), B, planes, scratch.data_ptr(), grad_w.data_ptr(),
                                                      torch.cuda.current_stream(xs.device).cuda_stream), "ippm_conv5x5_bf16_grad_weight")
         return grad_w
 
 
-def _head_scratch(lib, batch: int, n_actions: int, device, losses_only: bool = False):
-    """The scratch of the head entry points for ``batch``; ``losses_only``: its first part, all that the two losses use (ippmarl.h)."""
+def _loss_scratch(batch: int, device) -> torch.Tensor:
+    """The first part of the head entry points' scratch for ``batch``, all that the two losses use (ippmarl.h)."""
     from . import _ffi
-    if losses_only:
-        chunks = (batch + _ffi.HEAD_WGRAD_CHUNK - 1) // _ffi.HEAD_WGRAD_CHUNK
-        return torch.empty((chunks + 1) // 2 * 16, dtype=torch.uint8, device=device)
-    nbytes = ctypes.c_int64(0)
-    _ffi.check(lib.ippm_head_scratch_bytes(batch, n_actions, ctypes.addressof(nbytes)), "ippm_head_scratch_bytes")
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    chunks = (batch + _ffi.HEAD_WGRAD_CHUNK - 1) // _ffi.HEAD_WGRAD_CHUNK
+    return torch.empty((chunks + 1) // 2 * 16, dtype=torch.uint8, device=device)
 
 
 class _HeadBf16(torch.autograd.Function):
@@ -385,7 +380,7 @@ class _HeadBf16(torch.autograd.Function):
         gh, gw1, gw3 = torch.empty_like(hs), torch.empty_like(w1), torch.empty_like(w3)
         gb1 = torch.empty(256, dtype=hs.dtype, device=hs.device)
         gb3 = torch.empty(A, dtype=hs.dtype, device=hs.device)
-        scratch = _head_scratch(lib, B, A, hs.device)
+        scratch = _scratch("ippm_head_scratch_bytes", (B, A), hs.device)
         _ffi.check(lib.ippm_head_backward(g.data_ptr(), None, a1.data_ptr(), hs.data_ptr(), w1.data_ptr(), w3.data_ptr(), B, A, scratch.data_ptr(),
                                           gh.data_ptr(), gw1.data_ptr(), gb1.data_ptr(), gw3.data_ptr(), gb3.data_ptr(),
                                           torch.cuda.current_stream(hs.device).cuda_stream), "ippm_head_backward")
@@ -405,7 +400,7 @@ class _CriticLossBf16(torch.autograd.Function):
         loss = torch.empty((), dtype=q.dtype, device=q.device)
         q_chosen = torch.empty(B, dtype=q.dtype, device=q.device)
         dq = torch.empty_like(qs)
-        scratch = _head_scratch(lib, B, A, q.device, losses_only=True)
+        scratch = _loss_scratch(B, q.device)
         _ffi.check(lib.ippm_critic_loss(qs.data_ptr(), a32.data_ptr(), t32.data_ptr(), B, A, scratch.data_ptr(), loss.data_ptr(),
                                         q_chosen.data_ptr(), dq.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream), "ippm_critic_loss")
         ctx.save_for_backward(dq)
@@ -436,7 +431,7 @@ class _ActorLossBf16(torch.autograd.Function):
         adv = torch.empty(B, dtype=ls.dtype, device=ls.device)
         dlogits = torch.empty_like(ls)
         eps_dev = eps if isinstance(eps, torch.Tensor) else None
-        scratch = _head_scratch(lib, B, A, ls.device, losses_only=True)
+        scratch = _loss_scratch(B, ls.device)
         if probs_out is not None and (probs_out.dtype != ls.dtype or probs_out.numel() != B * A or not probs_out.is_contiguous()
                                       or probs_out.device != ls.device):
             raise _ffi.IppmError("_ActorLossBf16: probs_out must be a contiguous float32 [B,A] tensor on the logits' device")
