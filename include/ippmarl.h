@@ -400,7 +400,8 @@ int ippm_entropy_maps(ippm_ctx* ctx, const float* prob, const float* target, flo
                       float* se, float* grid, int64_t n, void* stream);
 
 /* ---- K7: COMA counterfactual advantage (actor/learner.py:55-95).  probs/q float [B,A], mask uint8 [B,A],
- * action int32 [B] -> advantage float [B], pi_tilde float [B,A] (may be NULL). */
+ * action int32 [B] -> advantage float [B], pi_tilde float [B,A] (may be NULL).  batch <= 0: returns 0, launches nothing and
+ * writes nothing. */
 int ippm_coma_advantage(ippm_ctx* ctx, const float* probs, const float* q, const uint8_t* mask,
                         const int32_t* action, float* advantage, float* pi_tilde, int32_t batch, void* stream);
 
@@ -687,7 +688,8 @@ int ippm_rollout_log_finalize(const void* log, int32_t n_waves, int32_t n_steps,
 
 /* ---- K8: BatchMemory.build_td_targets (batch_memory.py:120-162) over `chains` independent transition
  * lists of length `len` (row-major [chains,len]): reward float, done uint8, q_sel float = target critic
- * Q(s_t)[a_t] -> td_target, discounted_return float. */
+ * Q(s_t)[a_t] -> td_target, discounted_return float.  chains <= 0 or len <= 0: returns 0, launches nothing and writes nothing;
+ * chains * len above 2^31 - 1 is refused (-1 with a message, nothing launched). */
 int ippm_td_lambda(ippm_ctx* ctx, const float* reward, const uint8_t* done, const float* q_sel, float* td_target,
                    float* disc_return, int32_t chains, int32_t len, void* stream);
 

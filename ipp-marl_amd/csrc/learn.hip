@@ -25,9 +25,10 @@ k_coma_advantage(const float* __restrict__ probs, const float* __restrict__ q, c
 // accumulation stops ("leave") at the first transition whose predecessor is terminal.
 __global__ void k_td_lambda(const float* __restrict__ reward, const uint8_t* __restrict__ done, const float* __restrict__ q_sel,
                             float* __restrict__ td, float* __restrict__ dr, double gamma, double lam, int chains, int len) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= chains * len) return;
-  const int ch = idx / len, t = idx % len;
+  // (unsigned: chains * len may be anything up to 2^31 - 1, and the last workgroup's lanes count up to 255 past it)
+  const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (unsigned)(chains * len)) return;
+  const int ch = (int)(idx / (unsigned)len), t = (int)(idx % (unsigned)len);
   const float* r = reward + (size_t)ch * len;
   const uint8_t* d = done + (size_t)ch * len;
   const float* qs = q_sel + (size_t)ch * len;
@@ -40,6 +41,7 @@ __global__ void k_td_lambda(const float* __restrict__ reward, const uint8_t* __r
 extern "C" int ippm_coma_advantage(ippm_ctx* ctx, const float* probs, const float* q, const uint8_t* mask,
                                    const int32_t* action, float* advantage, float* pi_tilde, int32_t batch, void* stream) {
   if (!ctx || !probs || !q || !mask || !action || !advantage) { ippm_set_error("ippm_coma_advantage: null argument"); return -1; }
+  if (batch <= 0) return 0;
   const int A = ctx->cfg.n_actions;
   const int rows_per_block = 256 / 32;
   hipLaunchKernelGGL(k_coma_advantage, dim3((batch + rows_per_block - 1) / rows_per_block), dim3(256), 0, S_(stream), probs, q,
@@ -51,8 +53,13 @@ extern "C" int ippm_coma_advantage(ippm_ctx* ctx, const float* probs, const floa
 extern "C" int ippm_td_lambda(ippm_ctx* ctx, const float* reward, const uint8_t* done, const float* q_sel, float* td_target,
                               float* disc_return, int32_t chains, int32_t len, void* stream) {
   if (!ctx || !reward || !done || !q_sel || !td_target || !disc_return) { ippm_set_error("ippm_td_lambda: null argument"); return -1; }
+  if (chains <= 0 || len <= 0) return 0;
+  if ((int64_t)chains * len > INT32_MAX) {   // (the kernel indexes (chain, t) in int)
+    ippm_set_error("ippm_td_lambda: chains * len must not exceed 2^31 - 1");
+    return -1;
+  }
   const int total = chains * len;
-  hipLaunchKernelGGL(k_td_lambda, dim3((total + 255) / 256), dim3(256), 0, S_(stream), reward, done, q_sel, td_target,
+  hipLaunchKernelGGL(k_td_lambda, dim3((unsigned)(((int64_t)total + 255) / 256)), dim3(256), 0, S_(stream), reward, done, q_sel, td_target,
                      disc_return, ctx->cfg.gamma, ctx->cfg.lambda_, chains, len);
   IPPM_LAUNCH_CHECK("td_lambda");
   return 0;

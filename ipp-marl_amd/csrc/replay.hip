@@ -104,9 +104,10 @@ __global__ void __launch_bounds__(256) k_replay_store(const StoreArgs a) {
 __global__ void __launch_bounds__(256)
 k_td_lambda_buffer(const float* __restrict__ reward, const float* __restrict__ q_sel, float* __restrict__ td, float* __restrict__ dr,
                    double gamma, double lam, int T, int len, int C, int N, int per_agent) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= C * len) return;
-  const int c = idx % C, t = idx / C;
+  // (unsigned: C * len may be anything below 2^31, and the last workgroup's lanes count up to 255 past it)
+  const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (unsigned)(C * len)) return;
+  const int c = (int)(idx % (unsigned)C), t = (int)(idx / (unsigned)C);
   // rewards: [len, C] (one per agent) or [len, E] broadcast over the env's agents
   const float* r = per_agent ? reward + c : reward + c / N;
   const size_t rs = per_agent ? (size_t)C : (size_t)(C / N);
@@ -216,7 +217,8 @@ extern "C" int ippm_td_lambda_buffer(ippm_ctx* ctx, const float* reward, int32_t
   }
   const int C = n_envs * n_agents, len = waves * steps;
   const int total = C * len;
-  hipLaunchKernelGGL(k_td_lambda_buffer, dim3((total + 255) / 256), dim3(256), 0, S_(stream), reward, q_sel, td_target, disc_return,
+  hipLaunchKernelGGL(k_td_lambda_buffer, dim3((unsigned)(((int64_t)total + 255) / 256)), dim3(256), 0, S_(stream), reward, q_sel, td_target,
+                     disc_return,
                      ctx->cfg.gamma, ctx->cfg.lambda_, (int)steps, len, C, (int)n_agents, reward_per_agent ? 1 : 0);
   IPPM_LAUNCH_CHECK("ippm_td_lambda_buffer");
   return 0;
