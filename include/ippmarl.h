@@ -736,6 +736,30 @@ int ippm_replay_gather(const float* buf_state, const float* buf_obs, const int32
                        const float* buf_td, int64_t n, const int64_t* idx, int64_t count, int32_t n_actions, float* states, float* obs,
                        int32_t* actions, uint8_t* masks, float* td, int32_t* bad, void* stream);
 
+/* ---- the minibatch order of a training round, keyed like every other random stream ---------------------------------------------------
+ * ippm_minibatch_permutation writes idx[i] = pi(i) for i < n (int64, device): the permutation of [0, n) that the learners cut the
+ * minibatches of data pass `data_pass` of training round `round` from -- the `idx` of ippm_replay_gather.  A pure function of
+ * (seed; round, data_pass, n): no generator state exists anywhere.  round_dev (device int64[1], or NULL) is read IN THE KERNEL in place of
+ * `round` when given: a recorded round advances it on the device and needs no host-side argument.
+ *   pi: cycle-walking over a balanced Feistel network keyed by Philox.  k = bit length of n - 1 (0 for n = 1), h = max(1, ceil(k / 2)),
+ *   mask = 2^h - 1; the domain [0, 4^h) holds [0, n) and is smaller than 4n for n >= 3.  E(x): L = x >> h, R = x & mask; for r = 0 ..
+ *   IPPM_SHUFFLE_ROUNDS - 1:  f = Philox4x32-10(counter = (R, round & 0xFFFFFFFF, stream word(agent = r, stage = data_pass, domain = 4),
+ *   round >> 32), key = (seed & 0xFFFFFFFF, seed >> 32)).word0 & mask;  (L, R) <- (R, L ^ f);  E(x) = (L << h) | R.  The stream word is
+ *   (agent & 0xFF) | (stage & 0xFFFF) << 8 | domain << 24, as for the env's streams (domains 0-3: flips, actions, comm, terrain).
+ *   pi(i) = the first of E(i), E(E(i)), ... that is < n (i lies on a cycle of E that returns to [0, n)).  tests/shuffle_ref.py restates it.
+ *   Mixed team sizes: team_prefix (device int32[n_envs + 1], or NULL) = the exclusive prefix sums of the envs' flying agents; then n counts
+ *   FLYING transitions (a multiple of F = team_prefix[n_envs], read in the kernel), and rank q = pi(i) becomes a row of buffers in
+ *   [blocks, n_envs, n_agents] order: block = q / F, s = q % F, e = the env with team_prefix[e] <= s < team_prefix[e + 1] (binary search),
+ *   a = s - team_prefix[e], idx[i] = (block * n_envs + e) * n_agents + a -- the flying rows in ascending order, indexed by pi.  F < 1
+ *   writes -1 everywhere.  Without team_prefix, n_envs and n_agents are ignored.
+ * One lane per i, six Philox calls per point visited.  No context, no host synchronisation, no allocation, no scratch; launches on `stream`
+ * only and can be captured; writes idx[0 .. n) and nothing else.  -1 with ippm_last_error set, and nothing launched, for a NULL idx,
+ * n outside [1, 2^31), data_pass outside [0, 65536), team_prefix with n_envs < 1 or n_agents < 1, idx or round_dev not 8-byte aligned,
+ * team_prefix not 4-byte aligned. */
+#define IPPM_SHUFFLE_ROUNDS 6
+int ippm_minibatch_permutation(uint64_t seed, int64_t round, const int64_t* round_dev, int32_t data_pass, int64_t n,
+                               const int32_t* team_prefix, int32_t n_envs, int32_t n_agents, int64_t* idx, void* stream);
+
 /* ---- greedy information-gain planner (IG_baseline.py:222-325) and evaluation metrics -------------------------
  * ippm_ig_candidates (K9): gains float [E,N,A] = expected weighted entropy reduction over the footprint each valid action
  * leads to, / 1000 (get_individual_ig); masked actions get 0.  ippm_ig_select (K10): get_relative_ig +

@@ -131,6 +131,7 @@ PROTOTYPES = {
     "ippm_replay_store": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P],
     "ippm_td_lambda_buffer": [P, P, I32, P, P, P, I32, I32, I32, I32, P],
     "ippm_replay_gather": [P, P, P, P, P, I64, P, I64, I32, P, P, P, P, P, P, P],
+    "ippm_minibatch_permutation": [C.c_uint64, I64, P, I32, I64, P, I32, I32, P, P],
     "ippm_metrics_bytes": [I32, I64, I32, P],
     "ippm_metrics_critic": [P, I32, I32, P, P, P, P, P, P, I64, I32, P],
     "ippm_metrics_actor": [P, I32, I32, P, P, P, P, P, I64, I32, P],

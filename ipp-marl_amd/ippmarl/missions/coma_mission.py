@@ -23,7 +23,8 @@ from .missions import Mission
 
 class COMAMission(Mission):
     def __init__(self, params: Dict, writer, max_mean_episode_return: float = -100, n_envs: Optional[int] = None,
-                 log_dir: str = "logs", device: str = "cuda:0", eval_every: int = 50, eval_episodes: int = 50, **trainer_kwargs):
+                 log_dir: str = "logs", device: str = "cuda:0", eval_every: int = 50, eval_episodes: int = 50, state_every: int = 0,
+                 resume: Optional[str] = None, **trainer_kwargs):
         super().__init__(params, writer, max_mean_episode_return)
         self.num_episodes = params["experiment"]["missions"]["n_episodes"]
         self.batch_size = params["networks"]["batch_size"]
@@ -46,6 +47,13 @@ class COMAMission(Mission):
         self.episode_returns = []
         self.mode = "train"
         self.last_counts = None
+        # state_every = k > 0: every k updates the whole training state -- the trainer's (COMATrainer.state_dict) and this mission's own
+        # bookkeeping -- goes to log_dir/trainer_state.pt; resume = such a file: both halves are restored here, and execute() runs the
+        # updates that remain of ``n_episodes``.  best_model.pth is written as before.
+        self.state_every = int(state_every)
+        self._resumed_at = 0          # updates a resumed mission has behind it when its execute() starts
+        if resume is not None:
+            self.load_state(resume)
 
     def _eval_waves(self) -> int:
         return max(1, math.ceil(self.eval_episodes / self.n_envs))
@@ -91,9 +99,38 @@ class COMAMission(Mission):
         if self.training_step_idx in (300, 400, 500, 600):
             save_actor(actor_network, os.path.join(self.log_dir, f"best_model_{self.training_step_idx}.pth"))
 
+    STATE_FILE = "trainer_state.pt"
+
+    def save_state(self, path: Optional[str] = None) -> str:
+        """The trainer's state and the mission's bookkeeping in one ``torch.save`` file (default: log_dir/trainer_state.pt), written under
+        a temporary name and moved into place, so that a run killed while it writes leaves the previous file whole."""
+        path = path or os.path.join(self.log_dir, self.STATE_FILE)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        state = {"trainer": self.trainer.state_dict(),
+                 "mission": {"training_step_idx": int(self.training_step_idx), "environment_step_idx": int(self.environment_step_idx),
+                             "episode_returns": [float(r) for r in self.episode_returns],
+                             "max_mean_episode_return": float(self.max_mean_episode_return)}}
+        tmp = path + ".tmp"
+        torch.save(state, tmp)
+        os.replace(tmp, path)
+        return path
+
+    def load_state(self, path: str):
+        """Both halves of a ``save_state`` file back: the trainer continues bit for bit (COMATrainer.load_state_dict), the mission counts
+        on from the saved step, returns and best running mean."""
+        state = torch.load(path, map_location="cpu", weights_only=True)
+        self.trainer.load_state_dict(state["trainer"])
+        m = state["mission"]
+        self.training_step_idx, self.environment_step_idx = int(m["training_step_idx"]), int(m["environment_step_idx"])
+        self.episode_returns = [float(r) for r in m["episode_returns"]]
+        self.max_mean_episode_return = float(m["max_mean_episode_return"])
+        self._resumed_at = self.training_step_idx
+
     def execute(self):
         tr = self.trainer
-        for _ in range(self.num_episodes):
+        # (a resumed mission runs what remains of n_episodes; every other call runs n_episodes updates, as before)
+        remaining, self._resumed_at = max(0, self.num_episodes - self._resumed_at), 0
+        for _ in range(remaining):
             rollouts = []
             for _ in range(tr.waves_per_update):
                 wave = tr.rollout("train")
@@ -112,4 +149,6 @@ class COMAMission(Mission):
                     evals.append(tr.last_rollout)
                 self.add_to_tensorboard(evals)
                 self.mode = "train"
+            if self.state_every > 0 and self.training_step_idx % self.state_every == 0:
+                self.save_state()      # (after the evaluation: its waves number episodes too)
         return self.max_mean_episode_return

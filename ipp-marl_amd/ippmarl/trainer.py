@@ -18,6 +18,7 @@ from . import metrics_native
 from . import optim_native
 from . import replay_native
 from . import rollout_native
+from . import shuffle_native
 from .actor_native import NativeActor, resolve_mode
 from .learners import ActorLearner, CriticLearner
 from .networks import ActorNetwork, CriticNetwork, epsilon_schedule, resolve_conv2_update, resolve_head_update, resolve_trunk_update
@@ -29,11 +30,19 @@ class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
                  terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None,
-                 rollout_log: Optional[str] = None, metrics: Optional[str] = None,
+                 shuffle: Optional[str] = None, rollout_log: Optional[str] = None, metrics: Optional[str] = None,
                  buffer: Optional[str] = None,
                  actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, adam: Optional[str] = None,
                  head_update: Optional[str] = None, conv2_update: Optional[str] = None, trunk_update: Optional[str] = None):
         self.params = params
+        self.philox_seed = int(philox_seed)
+        # shuffle: where the minibatch order of update() comes from: "torch" (the default: torch.randperm, the device generator's hidden
+        # state) or "native" (shuffle_native.NativeShuffle: one launch of libippmarl per data pass writes the permutation keyed by
+        # (philox_seed; train_step on entry to update(), data pass) -- and, under team_sizes, maps it onto the flying transitions without the
+        # nonzero() of valid_transitions -- inside the recorded graph, which advances the round counter on the device); None reads
+        # IPPMARL_SHUFFLE.  Which rows a minibatch holds changes, nothing else of the round does.  Independent of the other switches.
+        self.shuffle = shuffle_native.resolve_mode(shuffle)
+        self._shuffle = None
         # metrics: who computes the 32 per-training-step scalars of update(diagnostics=True): "torch" (the default: the learners collect
         # per-minibatch records on the float32 path and ippmarl.metrics reduces them, launch by launch) or "native"
         # (metrics_native.NativeMetrics: libippmarl reduces the arrays of the round AS CONFIGURED -- native head, gathers, critic forward
@@ -157,6 +166,9 @@ class COMATrainer:
             self._replay = replay_native.NativeReplay(
                 self.env.ctx, (self.buf_obs, self.buf_state, self.buf_action, self.buf_mask, self.buf_reward),
                 (self.ret, self.abs_ret, self.team_ret), self.batch_number, last_agent=last if self.deepq else None)
+        if self.shuffle == "native":
+            flying = E * N if self.env.n_active is None else int(self.env.n_active.sum())
+            self._shuffle = shuffle_native.NativeShuffle(self.philox_seed, self.data_passes, W * T * flying, dev, self.env.n_active, E, N)
         if self.critic_inference == "native":
             self.critic_learner.inference = self._native_critic = critic_native.NativeCritic(self.critic, self.device)
             self._native_critic.reserve(W * T * E * N)
@@ -325,7 +337,8 @@ class COMATrainer:
         """Records the launch-bound round into hipGraphs: one graph per rollout step t of a training wave (the step number is an
         argument of several kernels, everything else -- episode numbers, epsilon, every array -- is read from fixed device
         buffers) and one graph for the whole update (TD targets + data_passes x batch_number minibatch steps of both nets, the
-        minibatch permutations read from a fixed buffer that update() refills).  Needs one eager round first (MIOpen's kernel
+        minibatch permutations read from a fixed buffer that update() refills -- or, shuffle="native", written by launches inside the
+        graph from a device round counter that its last node advances).  Needs one eager round first (MIOpen's kernel
         selection, allocator warm-up); waves_per_update = 1, hard target updates, one rank."""
         if not self.graphs:
             raise _ffi.IppmError("COMATrainer(graphs=True) is needed: captured optimizer steps keep their counters on the device")
@@ -363,7 +376,12 @@ class COMATrainer:
         self._graph_metrics = self.metrics == "native"
         if self._graph_metrics:
             self._native_metrics(n // self.batch_number)
-        self._perms = torch.stack([torch.randperm(n, device=self.device) for _ in range(self.data_passes)])
+        if self._shuffle is not None:
+            # the permutation launches are nodes of the graph and read the device round counter, which the graph's last node advances
+            self._perms = self._shuffle.idx
+            self._shuffle.set_round(self.train_step)
+        else:
+            self._perms = torch.stack([torch.randperm(n, device=self.device) for _ in range(self.data_passes)])
         self._loss_out = torch.zeros(2, device=self.device)
         filled, self.filled = self.filled, 1
         g = torch.cuda.CUDAGraph()
@@ -371,6 +389,8 @@ class COMATrainer:
             closs, aloss = self._update_compute(self._perms, self.eps_dev, self._graph_metrics)
             self._loss_out[0].copy_(closs)
             self._loss_out[1].copy_(aloss)
+            if self._shuffle is not None:
+                self._shuffle.advance()
         self.filled = filled
         torch.cuda.synchronize(self.device)
         for k, v in saved.items():   # capture does not execute; keep the env's state untouched in any case
@@ -427,9 +447,14 @@ class COMATrainer:
             self.critic_learner.update_target_network(self.train_step, 0)
             if self.critic_inference == "native":
                 self.native_target().sync()    # (the copy was written from the host: the recorded TD targets read the pack)
-            for dp in range(self.data_passes):
-                self._perms[dp].copy_(torch.randperm(n, device=self.device))
+            if self._shuffle is None:
+                for dp in range(self.data_passes):
+                    self._perms[dp].copy_(torch.randperm(n, device=self.device))
+            elif self._shuffle.host_round != self.train_step:
+                self._shuffle.set_round(self.train_step)      # (eager rounds since the last replay: they take the round by value)
             self._update_graph.replay()
+            if self._shuffle is not None:
+                self._shuffle.host_round = self.train_step + 1
             self.train_step += 1
             self.filled = 0
             closs, aloss = self._loss_out.tolist()
@@ -473,17 +498,22 @@ class COMATrainer:
     def _update_compute(self, perms, eps, diagnostics: bool):
         """The arithmetic of one round.  ``perms`` None: eager (draws the minibatch permutations, syncs the target network and
         counts train steps as it goes); a [data_passes, n] tensor: the form capture_graphs records (those host-side pieces are
-        done by update() around the replay)."""
+        done by update() around the replay).  shuffle="native": every pass's permutation is one launch here in either form, keyed by
+        the round by value (eager) or by the device counter (recorded)."""
         W, T, E, N = self.filled, self.T, self.E, self.N
         n = W * T * E * N
         eager = perms is None
+        round0 = self.train_step                     # the shuffle's round: train_step on entry (the eager form counts it up below)
         td, dr = self.td_targets()
         obs = self.buf_obs[:W].reshape(n, 11, 11, 7)
         states = self.buf_state[:W].reshape(n, 11, 11, 12)
         actions = self.buf_action[:W].reshape(n)
         masks = self.buf_mask[:W].reshape(n, self.A)
-        flying = self.valid_transitions(W)           # mixed team sizes: minibatches are drawn from the agents that fly
+        # mixed team sizes: minibatches are drawn from the agents that fly (shuffle="native": the permutation launch maps ranks to rows)
+        flying = self.valid_transitions(W) if self._shuffle is None else None
         nv = n if flying is None else int(flying.numel())
+        if self._shuffle is not None and self.env.n_active is not None:
+            nv = W * T * self._shuffle.flying
         bs = nv // self.batch_number
         closs = aloss = torch.zeros((), device=self.device)
         # buffer="native": ONE gather per minibatch b fills output set b % 2 of the replay (states, obs, actions, masks, td), issued right
@@ -514,7 +544,10 @@ class COMATrainer:
             return obs[idx[b]], actions[idx[b]], masks[idx[b]]
 
         for data_pass in range(self.data_passes):
-            perm = torch.randperm(nv, device=self.device) if eager else perms[data_pass]
+            if self._shuffle is not None:
+                perm = self._shuffle.permutation(data_pass, nv, round0 if eager else None)
+            else:
+                perm = torch.randperm(nv, device=self.device) if eager else perms[data_pass]
             if flying is not None:
                 perm = flying[perm]
             if eager:
@@ -766,3 +799,148 @@ class COMATrainer:
         """Whole-module pickle of the actor, the reference's checkpoint format (coma_mission.py:425-451)."""
         from .checkpoint import save_actor
         save_actor(self.actor, path)
+
+    # ---- trainer state: stop a run between two rounds, continue it bit for bit ------------------------------------------------------------
+    STATE_FORMAT = 1
+    SWITCHES = ("rollout_log", "metrics", "buffer", "actor_inference", "critic_inference", "adam", "head_update", "conv2_update",
+                "trunk_update", "shuffle")
+
+    def _state_modules(self):
+        return {"actor": self.actor, "critic": self.critic, "target_critic": self.critic_learner.target_critic,
+                "frozen_target": self.frozen_target}
+
+    def _state_optimizers(self):
+        return {"actor": self.actor_learner.optimizer, "critic": self.critic_learner.optimizer}
+
+    def fingerprint(self) -> Dict[str, object]:
+        """What a saved state must agree on with the trainer that loads it: the sizes, what numbers the episodes, and the two switches
+        whose state does not carry over (``adam``: the optimizer implementation; ``graphs``: the capturable Adam's arithmetic)."""
+        n_active = self.env.n_active
+        return {"n_envs": self.E, "n_agents": self.N, "n_actions": self.A, "T": self.T, "waves_per_update": self.waves_per_update,
+                "quirks": self.quirks, "philox_seed": self.philox_seed, "first_episode": self.first_episode, "rank": self.rank,
+                "world": self.world, "mission_type": str(self.params["experiment"]["missions"].get("type")),
+                "team_sizes": None if n_active is None else [int(v) for v in n_active.tolist()],
+                "adam": self.adam, "graphs": self.graphs}
+
+    def state_dict(self) -> Dict[str, object]:
+        """Everything a later round reads, as CPU tensors, numbers and strings (synchronises): the parameters of the actor, the critic,
+        the learner's target network and the construction-time target copy; both optimizers' ``state_dict()`` (torch.optim.Adam's
+        format from either implementation); the counters; the device generator's state (what shuffle="torch" draws from; shuffle="native"
+        has none to keep, its round counter is ``train_step``); the fingerprint and the switch values."""
+        cpu = lambda x: _map_tensors(x, lambda t: t.detach().to("cpu", copy=True))  # noqa: E731
+        return {"format": self.STATE_FORMAT, "fingerprint": self.fingerprint(),
+                "switches": {k: getattr(self, k) for k in self.SWITCHES},
+                "modules": {k: cpu(dict(m.state_dict())) for k, m in self._state_modules().items()},
+                "optimizers": {k: cpu(o.state_dict()) for k, o in self._state_optimizers().items()},
+                "counters": {"train_step": int(self.train_step), "wave": int(self.wave), "eval_wave": int(self.eval_wave),
+                             "step_replays": int(self.step_replays), "eps": float(self.eps),
+                             "shuffle_round": int(self.train_step)},
+                "rng": torch.cuda.get_rng_state(self.device).clone()}
+
+    def load_state_dict(self, state: Dict[str, object]):
+        """Continue from ``state`` (of ``state_dict()``): between rounds only, on a trainer whose fingerprint agrees.  Everything is written
+        IN PLACE (``copy_`` into the parameters, the optimizers' existing state tensors and the native Adam's blob), so graphs captured
+        before the load stay valid; modules and optimizer states are checked before the first write, so a state that does not fit leaves
+        the trainer as it was.  The device generator's state is restored for shuffle="torch" only.  Afterwards ``eps_dev`` is refilled, every inference pack is repacked (the parameters' version counters
+        have advanced) and the device round counter of shuffle="native" is set."""
+        if self.filled != 0:
+            raise _ffi.IppmError(f"load_state_dict: the buffer holds {self.filled} wave(s): a state is loaded between rounds (filled == 0)")
+        if state.get("format") != self.STATE_FORMAT:
+            raise _ffi.IppmError(f"load_state_dict: not a trainer state of format {self.STATE_FORMAT}")
+        mine, theirs = self.fingerprint(), state["fingerprint"]
+        for k, v in mine.items():
+            if k not in theirs or theirs[k] != v:
+                raise _ffi.IppmError(f"load_state_dict: the state's {k} is {theirs.get(k)!r}, this trainer's {v!r}")
+        modules = self._state_modules()
+        for name, module in modules.items():      # (checked first: nothing is written when a tensor does not fit)
+            saved = state["modules"][name]
+            own = module.state_dict()
+            if set(saved) != set(own) or any(tuple(saved[k].shape) != tuple(own[k].shape) for k in own):
+                raise _ffi.IppmError(f"load_state_dict: the state's {name} does not have this trainer's tensors")
+        for name, opt in self._state_optimizers().items():
+            _check_optimizer_state(name, opt, state["optimizers"][name])
+        with torch.no_grad():
+            for name, module in modules.items():
+                saved = state["modules"][name]
+                for k, t in list(module.named_parameters()) + list(module.named_buffers()):
+                    t.copy_(saved[k])
+        for name, opt in self._state_optimizers().items():
+            _load_optimizer_in_place(opt, state["optimizers"][name])
+        c = state["counters"]
+        self.train_step, self.wave = int(c["train_step"]), int(c["wave"])
+        self.eval_wave, self.step_replays = int(c["eval_wave"]), int(c["step_replays"])
+        self.eps = float(c["eps"])
+        self.eps_dev.fill_(self.eps)
+        if self._shuffle is not None:
+            self._shuffle.set_round(int(c["shuffle_round"]))
+        if self.shuffle == "torch" and state.get("rng") is not None:     # (the process-wide generator: only for who draws from it)
+            torch.cuda.set_rng_state(state["rng"].to("cpu", torch.uint8), self.device)
+        if self._native is not None and self._native.module is self.actor:
+            self._native.sync()
+        if self.critic_inference == "native":
+            self._native_critic.sync()
+            self.native_target().sync()
+
+    def save_state(self, path: str):
+        """``state_dict()`` as a plain ``torch.save`` (loads under ``torch.load(weights_only=True)``); between rounds only."""
+        if self.filled != 0:
+            raise _ffi.IppmError(f"save_state: the buffer holds {self.filled} wave(s): a state is saved between rounds (filled == 0)")
+        torch.save(self.state_dict(), path)
+
+    def load_state(self, path: str):
+        """``load_state_dict`` of a file written by ``save_state``."""
+        self.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+
+
+def _map_tensors(x, fn):
+    """``x`` with ``fn`` applied to every tensor inside its dicts, lists and tuples (the containers become plain dicts, lists, tuples)."""
+    if isinstance(x, torch.Tensor):
+        return fn(x)
+    if isinstance(x, dict):
+        return {k: _map_tensors(v, fn) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_map_tensors(v, fn) for v in x)
+    return x
+
+
+def _saved_entries(opt, saved):
+    """{id(parameter): its entry of ``saved["state"]`` or None} for the parameters of ``opt``'s one group."""
+    params = opt.param_groups[0]["params"]
+    return {id(p): saved["state"].get(k) for p, k in zip(params, saved["param_groups"][0]["params"])}
+
+
+def _check_optimizer_state(name, opt, saved):
+    """Raises unless ``saved`` (torch.optim.Adam's format) fits ``opt``: one group over as many parameters, moments of the parameters'
+    shapes, and -- for a torch optimizer that has stepped, which is written in place -- entries for exactly the parameters it has stepped."""
+    params = opt.param_groups[0]["params"]
+    groups = saved["param_groups"]
+    if len(groups) != 1 or len(groups[0]["params"]) != len(params):
+        raise _ffi.IppmError(f"load_state_dict: the {name} optimizer's state is over another parameter list")
+    entries = _saved_entries(opt, saved)
+    for p in params:
+        e = entries[id(p)]
+        if e is not None and any(k not in e or tuple(e[k].shape) != tuple(p.shape) for k in ("exp_avg", "exp_avg_sq")):
+            raise _ffi.IppmError(f"load_state_dict: the {name} optimizer's moments do not have the parameters' shapes")
+    if not isinstance(opt, optim_native.NativeAdam) and opt.state:
+        want = {i for i, e in entries.items() if e is not None}
+        if want and want != {id(p) for p in opt.state}:
+            raise _ffi.IppmError(f"load_state_dict: the {name} optimizer's state steps other parameters than this trainer's has stepped")
+
+
+def _load_optimizer_in_place(opt, saved):
+    """``saved`` (checked by ``_check_optimizer_state``) into ``opt`` without replacing a tensor that a captured graph may hold: NativeAdam
+    writes views of its blob; a torch optimizer that has stepped gets ``copy_`` into its state tensors; one that never stepped has no state
+    tensor anybody could hold, and takes ``load_state_dict``."""
+    if isinstance(opt, optim_native.NativeAdam) or not opt.state:
+        opt.load_state_dict(saved)
+        return
+    entries = _saved_entries(opt, saved)
+    with torch.no_grad():
+        for p, st in opt.state.items():
+            e = entries[id(p)]
+            for k, v in st.items():
+                if torch.is_tensor(v):
+                    if e is None:
+                        v.zero_()           # (a state saved before the first step: zero moments at step 0 are Adam's initial state)
+                    else:
+                        v.copy_(e[k])
