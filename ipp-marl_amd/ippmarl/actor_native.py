@@ -12,16 +12,16 @@ from typing import Optional
 
 import torch
 
-from . import _ffi
-from .native_net import MODES, NativeNet, resolve  # noqa: F401
+from . import _ffi, switches
+from .native_net import MODES, NativeNet  # noqa: F401
 
-ENV_VAR = "IPPMARL_ACTOR_INFERENCE"
+ENV_VAR = switches.TABLE["actor_inference"].env_var
 
 
 def resolve_mode(actor_inference: Optional[str] = None) -> str:
     """The actor's inference path: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises.
     (The critic's switch: critic_native.resolve_mode.)"""
-    return resolve(actor_inference, ENV_VAR, "actor")
+    return switches.resolve("actor_inference", actor_inference)
 
 
 class NativeActor(NativeNet):

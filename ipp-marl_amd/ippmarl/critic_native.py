@@ -14,15 +14,15 @@ from typing import Optional
 
 import torch
 
-from . import _ffi
-from .native_net import MODES, NativeNet, resolve  # noqa: F401
+from . import _ffi, switches
+from .native_net import MODES, NativeNet  # noqa: F401
 
-ENV_VAR = "IPPMARL_CRITIC_INFERENCE"
+ENV_VAR = switches.TABLE["critic_inference"].env_var
 
 
 def resolve_mode(critic_inference: Optional[str] = None) -> str:
     """The critic's inference path: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises."""
-    return resolve(critic_inference, ENV_VAR, "critic")
+    return switches.resolve("critic_inference", critic_inference)
 
 
 class NativeCritic(NativeNet):

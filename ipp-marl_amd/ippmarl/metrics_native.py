@@ -13,16 +13,14 @@ atomics -- the same bits whatever the blob held, in whatever order the slots wer
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, Optional, Sequence
 
 import torch
 
-from . import _ffi
+from . import _ffi, switches
 from .metrics import LAYER_TAGS
 
-ENV_VAR = "IPPMARL_METRICS"
-MODES = ("torch", "native")
+ENV_VAR, MODES = switches.TABLE["metrics"][:2]
 SCALARS = 32        # IPPM_METRICS_SCALARS
 CHUNK = 256         # IPPM_METRICS_CHUNK
 
@@ -40,10 +38,7 @@ assert len(KEYS) == SCALARS
 
 def resolve_mode(metrics: Optional[str] = None) -> str:
     """The trainer's diagnostics path: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises."""
-    mode = metrics if metrics is not None else os.environ.get(ENV_VAR, "") or "torch"
-    if mode not in MODES:
-        raise ValueError(f"metrics must be one of {MODES}, got {mode!r}")
-    return mode
+    return switches.resolve("metrics", metrics)
 
 
 def _f32(x: torch.Tensor, numel: int, what: str, device) -> torch.Tensor:

@@ -9,8 +9,6 @@ starts recording.  GPU only: there is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import Optional
 
 import torch
 
@@ -18,15 +16,6 @@ from . import _ffi
 
 MODES = ("torch", "native")
 _LAYERS = ("conv1", "conv2", "conv3", "fc1", "fc3")   # fc2 is never used by the network (networks._ConvTrunk)
-
-
-def resolve(value: Optional[str], env_var: str, what: str) -> str:
-    """A "torch" / "native" switch (the inference paths; "adam": the learners' optimizer): the argument, else the environment variable,
-    else "torch"; anything but "torch" / "native" raises."""
-    mode = value if value is not None else os.environ.get(env_var, "") or "torch"
-    if mode not in MODES:
-        raise ValueError(f"{what if what == 'adam' else what + ' inference'} must be one of {MODES}, got {mode!r}")
-    return mode
 
 
 class NativeNet:

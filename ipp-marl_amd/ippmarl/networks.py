@@ -17,6 +17,8 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
+from . import switches
+
 # MIOpen's exhaustive solver search (needed: its fast mode picks kernels that make a COMA update 6x slower) also times the
 # naive reference convolutions, which take 0.3-0.5 s per run on the 12k-sample minibatches: 40 s of warm-up per process
 # for nothing.  Leave them out of the search unless the user says otherwise.
@@ -35,17 +37,13 @@ CONV2_BWD_DATA_AS_GEMM = os.environ.get("IPPMARL_CONV2_BWD_GEMM", "1") != "0"
 # conv2 of a forward-with-gradient pass: "float32" (the library's convolution, the default) or "bf16" (libippmarl's matrix-core kernels,
 # see _Conv4x4Bf16).  The mode belongs to the CALLER of the forward -- a learner enters conv2_update(mode) around it -- and is neither
 # process-global nor stored in the module: whole-module pickles are the checkpoint format.
-CONV2_UPDATE_MODES = ("float32", "bf16")
-CONV2_UPDATE_ENV = "IPPMARL_CONV2_UPDATE"
+CONV2_UPDATE_ENV, CONV2_UPDATE_MODES = switches.TABLE["conv2_update"][:2]
 _CONV2_UPDATE: "contextvars.ContextVar[str]" = contextvars.ContextVar("ippmarl_conv2_update", default="float32")
 
 
 def resolve_conv2_update(conv2_update: Optional[str] = None) -> str:
     """The update's conv2 path: the argument, else IPPMARL_CONV2_UPDATE, else "float32"; anything but "float32" / "bf16" raises."""
-    mode = conv2_update if conv2_update is not None else os.environ.get(CONV2_UPDATE_ENV, "") or "float32"
-    if mode not in CONV2_UPDATE_MODES:
-        raise ValueError(f"conv2 update must be one of {CONV2_UPDATE_MODES}, got {mode!r}")
-    return mode
+    return switches.resolve("conv2_update", conv2_update)
 
 
 @contextlib.contextmanager
@@ -64,17 +62,13 @@ def conv2_update(mode: str):
 # conv1, conv2 and conv3 of a forward-with-gradient pass: "float32" (the default: whatever conv2_update says for conv2, the float32
 # library for the rest) or "bf16" (conv1 through _Conv5x5Bf16, conv2 through _Conv4x4Bf16 whatever conv2_update says, conv3 through
 # _Conv3Bf16).  The rules of the conv2 switch: the mode belongs to the caller of the forward and is never stored in the module.
-TRUNK_UPDATE_MODES = ("float32", "bf16")
-TRUNK_UPDATE_ENV = "IPPMARL_TRUNK_UPDATE"
+TRUNK_UPDATE_ENV, TRUNK_UPDATE_MODES = switches.TABLE["trunk_update"][:2]
 _TRUNK_UPDATE: "contextvars.ContextVar[str]" = contextvars.ContextVar("ippmarl_trunk_update", default="float32")
 
 
 def resolve_trunk_update(trunk_update: Optional[str] = None) -> str:
     """The update's trunk path: the argument, else IPPMARL_TRUNK_UPDATE, else "float32"; anything but "float32" / "bf16" raises."""
-    mode = trunk_update if trunk_update is not None else os.environ.get(TRUNK_UPDATE_ENV, "") or "float32"
-    if mode not in TRUNK_UPDATE_MODES:
-        raise ValueError(f"trunk update must be one of {TRUNK_UPDATE_MODES}, got {mode!r}")
-    return mode
+    return switches.resolve("trunk_update", trunk_update)
 
 
 @contextlib.contextmanager
@@ -93,17 +87,13 @@ def trunk_update(mode: str):
 # Everything behind conv3 of a forward-with-gradient pass -- fc1, ReLU, fc3 (and, in the learners, the loss): "float32" (the default:
 # PyTorch's GEMMs and elementwise passes) or "bf16" (libippmarl's head kernels, see _HeadBf16).  The rules of the other two switches:
 # the mode belongs to the caller of the forward and is never stored in the module.  Independent of conv2_update and trunk_update.
-HEAD_UPDATE_MODES = ("float32", "bf16")
-HEAD_UPDATE_ENV = "IPPMARL_HEAD_UPDATE"
+HEAD_UPDATE_ENV, HEAD_UPDATE_MODES = switches.TABLE["head_update"][:2]
 _HEAD_UPDATE: "contextvars.ContextVar[str]" = contextvars.ContextVar("ippmarl_head_update", default="float32")
 
 
 def resolve_head_update(head_update: Optional[str] = None) -> str:
     """The update's head path: the argument, else IPPMARL_HEAD_UPDATE, else "float32"; anything but "float32" / "bf16" raises."""
-    mode = head_update if head_update is not None else os.environ.get(HEAD_UPDATE_ENV, "") or "float32"
-    if mode not in HEAD_UPDATE_MODES:
-        raise ValueError(f"head update must be one of {HEAD_UPDATE_MODES}, got {mode!r}")
-    return mode
+    return switches.resolve("head_update", head_update)
 
 
 @contextlib.contextmanager

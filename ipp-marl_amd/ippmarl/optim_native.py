@@ -14,10 +14,10 @@ from typing import Iterable, Optional
 
 import torch
 
-from . import _ffi
-from .native_net import MODES, NativeNet, _LAYERS, resolve  # noqa: F401
+from . import _ffi, switches
+from .native_net import MODES, NativeNet, _LAYERS  # noqa: F401
 
-ENV_VAR = "IPPMARL_ADAM"
+ENV_VAR = switches.TABLE["adam"].env_var
 ZERO_GRAD = 1           # IPPM_ADAM_ZERO_GRAD
 MAX_TENSORS = 16        # IPPM_ADAM_MAX_TENSORS
 COUNTER_BYTES = 64      # the counters block in front of the moments (the layout is documented in include/ippmarl.h)
@@ -25,7 +25,7 @@ COUNTER_BYTES = 64      # the counters block in front of the moments (the layout
 
 def resolve_mode(adam: Optional[str] = None) -> str:
     """The learners' optimizer: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises."""
-    return resolve(adam, ENV_VAR, "adam")
+    return switches.resolve("adam", adam)
 
 
 def used_parameters(module):

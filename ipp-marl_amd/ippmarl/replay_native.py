@@ -9,23 +9,18 @@ per-(chain, t) code at other strides -- a round with ``buffer="native"`` leaves 
 ``buffer`` / ``IPPMARL_BUFFER`` select the implementation: "torch" (default) or "native".  GPU only: there is no CPU fallback."""
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 
-from . import _ffi
+from . import _ffi, switches
 
-ENV_VAR = "IPPMARL_BUFFER"
-MODES = ("torch", "native")
+ENV_VAR, MODES = switches.TABLE["buffer"][:2]
 
 
 def resolve_mode(buffer: Optional[str] = None) -> str:
     """The trainer's replay buffer: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises."""
-    mode = buffer if buffer is not None else os.environ.get(ENV_VAR, "") or "torch"
-    if mode not in MODES:
-        raise ValueError(f"buffer must be one of {MODES}, got {mode!r}")
-    return mode
+    return switches.resolve("buffer", buffer)
 
 
 class NativeReplay:

@@ -14,15 +14,13 @@ the same bits whatever the blob held, in whatever order the steps were called.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _ffi
+from . import _ffi, switches
 
-ENV_VAR = "IPPMARL_ROLLOUT_LOG"
-MODES = ("torch", "native")
+ENV_VAR, MODES = switches.TABLE["rollout_log"][:2]
 SCALARS = 12        # IPPM_ROLLOUT_SCALARS
 COUNTS = 65         # IPPM_ROLLOUT_COUNTS: [0,32) actions, [32,64) altitude levels, [64] entries counted in no bin
 ROWS = 1024         # IPPM_ROLLOUT_ROWS: (env, agent) rows of one workgroup of the step launch
@@ -35,10 +33,7 @@ assert len(KEYS) == SCALARS
 
 def resolve_mode(rollout_log: Optional[str] = None) -> str:
     """The trainer's rollout-log path: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises."""
-    mode = rollout_log if rollout_log is not None else os.environ.get(ENV_VAR, "") or "torch"
-    if mode not in MODES:
-        raise ValueError(f"rollout_log must be one of {MODES}, got {mode!r}")
-    return mode
+    return switches.resolve("rollout_log", rollout_log)
 
 
 class NativeRolloutLog:

@@ -15,24 +15,19 @@ minibatch positions do not).
 ``shuffle`` / ``IPPMARL_SHUFFLE`` select the implementation: "torch" (default) or "native".  GPU only: there is no CPU fallback."""
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 
-from . import _ffi
+from . import _ffi, switches
 
-ENV_VAR = "IPPMARL_SHUFFLE"
-MODES = ("torch", "native")
+ENV_VAR, MODES = switches.TABLE["shuffle"][:2]
 MAX_PASSES = 65536      # data_pass is the 16-bit stage field of the Philox stream word
 
 
 def resolve_mode(shuffle: Optional[str] = None) -> str:
     """The trainer's minibatch shuffle: the argument, else the environment variable, else "torch"; anything but "torch" / "native" raises."""
-    mode = shuffle if shuffle is not None else os.environ.get(ENV_VAR, "") or "torch"
-    if mode not in MODES:
-        raise ValueError(f"shuffle must be one of {MODES}, got {mode!r}")
-    return mode
+    return switches.resolve("shuffle", shuffle)
 
 
 class NativeShuffle:

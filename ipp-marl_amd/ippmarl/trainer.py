@@ -18,12 +18,14 @@ from . import metrics_native
 from . import optim_native
 from . import replay_native
 from . import rollout_native
+from . import round as seams
 from . import shuffle_native
+from . import switches
 from .actor_native import NativeActor, resolve_mode
 from .learners import ActorLearner, CriticLearner
 from .networks import ActorNetwork, CriticNetwork, epsilon_schedule, resolve_conv2_update, resolve_head_update, resolve_trunk_update
 from .parallel import GradAllReducer, broadcast_module, episode_ids
-from .vec_env import VecEnv, POLICY_ARGMAX, POLICY_SAMPLE
+from .vec_env import VecEnv, POLICY_ARGMAX, POLICY_EXPLICIT, POLICY_SAMPLE, POLICY_UNIFORM
 
 
 class COMATrainer:
@@ -36,63 +38,24 @@ class COMATrainer:
                  head_update: Optional[str] = None, conv2_update: Optional[str] = None, trunk_update: Optional[str] = None):
         self.params = params
         self.philox_seed = int(philox_seed)
-        # shuffle: where the minibatch order of update() comes from: "torch" (the default: torch.randperm, the device generator's hidden
-        # state) or "native" (shuffle_native.NativeShuffle: one launch of libippmarl per data pass writes the permutation keyed by
-        # (philox_seed; train_step on entry to update(), data pass) -- and, under team_sizes, maps it onto the flying transitions without the
-        # nonzero() of valid_transitions -- inside the recorded graph, which advances the round counter on the device); None reads
-        # IPPMARL_SHUFFLE.  Which rows a minibatch holds changes, nothing else of the round does.  Independent of the other switches.
-        self.shuffle = shuffle_native.resolve_mode(shuffle)
-        self._shuffle = None
-        # metrics: who computes the 32 per-training-step scalars of update(diagnostics=True): "torch" (the default: the learners collect
-        # per-minibatch records on the float32 path and ippmarl.metrics reduces them, launch by launch) or "native"
-        # (metrics_native.NativeMetrics: libippmarl reduces the arrays of the round AS CONFIGURED -- native head, gathers, critic forward
-        # and Adam stay on -- inside the recorded graph, read with one device-to-host copy); None reads IPPMARL_METRICS.  Independent of
-        # the other switches; metrics observe a round and never change it.
-        self.metrics = metrics_native.resolve_mode(metrics)
-        self._metrics = None
+        # the ten opt-in paths (switches.TABLE; None reads the switch's environment variable): resolved before anything needs the GPU;
+        # what each selects is described in its module's docstring and in INTEGRATION.md
+        self.shuffle = shuffle_native.resolve_mode(shuffle)                       # where the minibatch order of update() comes from
+        self.metrics = metrics_native.resolve_mode(metrics)                       # who computes update(diagnostics=True)'s 32 scalars
+        self.buffer = replay_native.resolve_mode(buffer)                          # who writes, chains and gathers the buf_* tensors
+        self.rollout_log = rollout_native.resolve_mode(rollout_log)               # who computes the log a ``keep_rollout_log`` trainer keeps
+        self.adam = optim_native.resolve_mode(adam)                               # the learners' optimizer
+        self.head_update = resolve_head_update(head_update)                       # fc1, fc3 and the losses of the forward with gradients
+        self.trunk_update = resolve_trunk_update(trunk_update)                    # conv1, conv2, conv3 of the forward with gradients
+        self.conv2_update = resolve_conv2_update(conv2_update)                    # conv2 alone of the forward with gradients
+        self.actor_inference = resolve_mode(actor_inference)                      # every no-grad use of the actor
+        self.critic_inference = critic_native.resolve_mode(critic_inference)      # the TD targets and the post-step Q
+        self._shuffle = self._metrics = self._replay = self._rollout_log = self._native = None
+        self._native_critic = self._native_target = None
         self._graph_metrics = False
-        # buffer: "torch" (the default: copy_, += and index operations) or "native" (replay_native.NativeReplay: one launch of libippmarl
-        # stores a rollout step's transition and advances the returns, one builds the TD targets from buffer order, one gathers a minibatch
-        # of all five training arrays); None reads IPPMARL_BUFFER.  Who writes the buf_* tensors and the returns changes, nothing they hold
-        # does.  Independent of the other switches.
-        self.buffer = replay_native.resolve_mode(buffer)
-        self._replay = None
-        # rollout_log: who computes the per-round rollout log a trainer with ``keep_rollout_log`` keeps (the mission's return / reward
-        # statistics and its action and altitude counts): "torch" (the default: three clones per step into ``last_rollout``, launch by
-        # launch -- such a trainer never replays its recorded rollout -- and host reductions by the caller) or "native"
-        # (rollout_native.NativeRolloutLog: one launch of libippmarl per rollout step, recorded into every step graph, so the recorded
-        # rollout replays whether the log is kept or not; read_rollout_log() closes it with one launch and one device-to-host copy, and
-        # ``last_rollout`` is not filled); None reads IPPMARL_ROLLOUT_LOG.  Independent of the other switches; the log observes a rollout
-        # and never changes it.
-        self.rollout_log = rollout_native.resolve_mode(rollout_log)
-        self._rollout_log = None
         self.rollout_log_waves = None     # waves the native log holds (None: waves_per_update); set it before the first logged rollout
         self.eval_wave = 0                # the native log's slot of the next eval wave; read_rollout_log("eval", ...) rewinds it
         self.step_replays = 0             # recorded rollout steps replayed so far
-        # adam: "torch" (torch.optim.Adam, the default) or "native" (optim_native.NativeAdam: one launch of libippmarl steps a net, clears
-        # its gradients and rewrites the inference pack where one is kept -- the same kernel whether ``graphs`` is set or not); None reads
-        # IPPMARL_ADAM.  Independent of the other switches.
-        self.adam = optim_native.resolve_mode(adam)
-        # head_update: "float32" (the default) or "bf16": fc1, ReLU, fc3, the loss and their gradients of both learners' forward-with-
-        # gradient pass through libippmarl's head kernels (networks._HeadBf16, _CriticLossBf16, _ActorLossBf16); None reads
-        # IPPMARL_HEAD_UPDATE.  Independent of the other switches; every no-grad forward and the diagnostics' minibatches are float32.
-        self.head_update = resolve_head_update(head_update)
-        # trunk_update: "float32" (the default) or "bf16": conv1 (networks._Conv5x5Bf16), conv2 and conv3 (networks._Conv3Bf16) of both
-        # learners' forward-with-gradient pass and their gradients on the bf16 matrix cores, whatever conv2_update says; None reads
-        # IPPMARL_TRUNK_UPDATE.  fc1, fc3, Adam, every no-grad forward and the diagnostics' extra forwards are float32 either way.
-        self.trunk_update = resolve_trunk_update(trunk_update)
-        # conv2_update: "float32" (the default) or "bf16": conv2's forward-with-gradient pass and both its gradients, in both learners,
-        # on the bf16 matrix cores (networks._Conv4x4Bf16); None reads IPPMARL_CONV2_UPDATE.  Every other layer, Adam and the
-        # diagnostics' extra forwards are float32 either way.
-        self.conv2_update = resolve_conv2_update(conv2_update)
-        # actor_inference: "torch" (the float32 module, the default) or "native" (libippmarl's bf16 matrix-core forward for every
-        # no-grad use of the actor: actor_native.NativeActor); None reads IPPMARL_ACTOR_INFERENCE.  The update is float32 either way.
-        self.actor_inference = resolve_mode(actor_inference)
-        self._native = None
-        # critic_inference: the same switch for the no-grad uses of a critic (critic_native.NativeCritic): the TD targets and the
-        # post-step Q of every critic minibatch; None reads IPPMARL_CRITIC_INFERENCE.  The critic's loss and gradients are float32 either way.
-        self.critic_inference = critic_native.resolve_mode(critic_inference)
-        self._native_critic = self._native_target = None
         # team_sizes: mixed team sizes in one batch (VecEnv): the transitions of agents that do not fly never enter a minibatch
         self.env = VecEnv(params, n_envs, device=device, philox_seed=philox_seed, terrain=terrain, team_sizes=team_sizes)
         # mission type DeepQ (coma_wrapper.py:113-171): every agent's transition carries ITS information gain (VecEnv.agent_reward, on
@@ -169,6 +132,7 @@ class COMATrainer:
         if self.shuffle == "native":
             flying = E * N if self.env.n_active is None else int(self.env.n_active.sum())
             self._shuffle = shuffle_native.NativeShuffle(self.philox_seed, self.data_passes, W * T * flying, dev, self.env.n_active, E, N)
+        self._order = seams.NativeOrder(self, self._shuffle) if self._shuffle is not None else seams.TorchOrder(self)
         if self.critic_inference == "native":
             self.critic_learner.inference = self._native_critic = critic_native.NativeCritic(self.critic, self.device)
             self._native_critic.reserve(W * T * E * N)
@@ -227,28 +191,27 @@ class COMATrainer:
         obs = env.build_observations(t)
         probs = self._act(obs, eps)
         reward, done, state = env.steps(t, policy=policy, probs=probs.view(self.E, self.N, self.A))
+        team = reward
         if self._replay is not None:
             # one launch: the transition into slot (w, t) and one float32 add on each of ret, abs_ret, team_ret
             self._replay.store(w, t, obs, state, env.action, env.mask, reward, env.agent_reward if self.deepq else None, store=store)
-            if self._log_wave is not None:
-                self._log_step(t, reward)
-                return reward
-            # (the returned reward is read by rollout()'s log only: the DeepQ gather is spent when that log is kept)
-            return self.last_agent_reward() if self.deepq and self.keep_rollout_log else reward
+            # (the returned reward is read by rollout()'s torch log only: the DeepQ gather is spent when that log is kept)
+            if self.deepq and self.keep_rollout_log and self._log_wave is None:
+                reward = self.last_agent_reward()
+        else:
+            if self.deepq:
+                reward = self.last_agent_reward()
+            if store:
+                self.buf_obs[w, t].copy_(obs)
+                self.buf_state[w, t].copy_(state)
+                self.buf_action[w, t].copy_(env.action)
+                self.buf_mask[w, t].copy_(env.mask)
+                self.buf_reward[w, t].copy_(env.agent_reward[..., 0] if self.deepq else reward[:, 0])
+            self.ret += reward[:, 0]
+            self.abs_ret += reward[:, 1]
+            self.team_ret += team[:, 0]
         if self._log_wave is not None:
-            self._log_step(t, reward)
-        team = reward
-        if self.deepq:
-            reward = self.last_agent_reward()
-        if store:
-            self.buf_obs[w, t].copy_(obs)
-            self.buf_state[w, t].copy_(state)
-            self.buf_action[w, t].copy_(env.action)
-            self.buf_mask[w, t].copy_(env.mask)
-            self.buf_reward[w, t].copy_(env.agent_reward[..., 0] if self.deepq else reward[:, 0])
-        self.ret += reward[:, 0]
-        self.abs_ret += reward[:, 1]
-        self.team_ret += team[:, 0]
+            self._log_step(t, team)
         return reward
 
     def _log_step(self, t: int, reward: torch.Tensor):
@@ -376,21 +339,15 @@ class COMATrainer:
         self._graph_metrics = self.metrics == "native"
         if self._graph_metrics:
             self._native_metrics(n // self.batch_number)
-        if self._shuffle is not None:
-            # the permutation launches are nodes of the graph and read the device round counter, which the graph's last node advances
-            self._perms = self._shuffle.idx
-            self._shuffle.set_round(self.train_step)
-        else:
-            self._perms = torch.stack([torch.randperm(n, device=self.device) for _ in range(self.data_passes)])
+        perms = self._order.capture(n)      # (the fixed buffer the recorded data passes read their order from)
         self._loss_out = torch.zeros(2, device=self.device)
         filled, self.filled = self.filled, 1
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=stream):
-            closs, aloss = self._update_compute(self._perms, self.eps_dev, self._graph_metrics)
+            closs, aloss = self._update_compute(perms, self.eps_dev, self._graph_metrics)
             self._loss_out[0].copy_(closs)
             self._loss_out[1].copy_(aloss)
-            if self._shuffle is not None:
-                self._shuffle.advance()
+            self._order.end_capture()
         self.filled = filled
         torch.cuda.synchronize(self.device)
         for k, v in saved.items():   # capture does not execute; keep the env's state untouched in any case
@@ -443,26 +400,17 @@ class COMATrainer:
         assert W > 0, "update() needs at least one rollout wave"
         n = W * T * E * N
         if self._update_graph is not None and W == 1 and (not diagnostics or self._graph_metrics):
-            # the recorded round: hard target copy (a host-side decision) first, fresh permutations into the graph's buffer, replay
+            # the recorded round: hard target copy (a host-side decision) first, the round's minibatch order made ready, replay
             self.critic_learner.update_target_network(self.train_step, 0)
             if self.critic_inference == "native":
                 self.native_target().sync()    # (the copy was written from the host: the recorded TD targets read the pack)
-            if self._shuffle is None:
-                for dp in range(self.data_passes):
-                    self._perms[dp].copy_(torch.randperm(n, device=self.device))
-            elif self._shuffle.host_round != self.train_step:
-                self._shuffle.set_round(self.train_step)      # (eager rounds since the last replay: they take the round by value)
+            self._order.before_replay(n)
             self._update_graph.replay()
-            if self._shuffle is not None:
-                self._shuffle.host_round = self.train_step + 1
+            self._order.after_replay()
             self.train_step += 1
-            self.filled = 0
             closs, aloss = self._loss_out.tolist()
-            if diagnostics:
-                self.last_diagnostics = self._metrics.read()
-            return {"critic_loss": closs, "actor_loss": aloss, "transitions": n * self.world,
-                    "adam_steps": 2 * self.data_passes * self.batch_number, "train_step": self.train_step}
-        closs, aloss = self._update_compute(None, self.eps_dev if self.graphs else self.eps, diagnostics)
+        else:
+            closs, aloss = self._update_compute(None, self.eps_dev if self.graphs else self.eps, diagnostics)
         if diagnostics and self.metrics == "native":
             self.last_diagnostics = self._metrics.read()
         self.filled = 0
@@ -497,126 +445,63 @@ class COMATrainer:
 
     def _update_compute(self, perms, eps, diagnostics: bool):
         """The arithmetic of one round.  ``perms`` None: eager (draws the minibatch permutations, syncs the target network and
-        counts train steps as it goes); a [data_passes, n] tensor: the form capture_graphs records (those host-side pieces are
-        done by update() around the replay).  shuffle="native": every pass's permutation is one launch here in either form, keyed by
-        the round by value (eager) or by the device counter (recorded)."""
-        W, T, E, N = self.filled, self.T, self.E, self.N
-        n = W * T * E * N
+        counts train steps as it goes); what ``_order.capture`` returned: the form capture_graphs records (those host-side pieces are
+        done by update() around the replay).  Where the order, the minibatches' rows and the diagnostics come from is behind the three
+        seams of ippmarl.round, chosen here once per round."""
+        W = self.filled
         eager = perms is None
-        round0 = self.train_step                     # the shuffle's round: train_step on entry (the eager form counts it up below)
         td, dr = self.td_targets()
-        obs = self.buf_obs[:W].reshape(n, 11, 11, 7)
-        states = self.buf_state[:W].reshape(n, 11, 11, 12)
-        actions = self.buf_action[:W].reshape(n)
-        masks = self.buf_mask[:W].reshape(n, self.A)
-        # mixed team sizes: minibatches are drawn from the agents that fly (shuffle="native": the permutation launch maps ranks to rows)
-        flying = self.valid_transitions(W) if self._shuffle is None else None
-        nv = n if flying is None else int(flying.numel())
-        if self._shuffle is not None and self.env.n_active is not None:
-            nv = W * T * self._shuffle.flying
+        nv = self._order.begin_round(W)
         bs = nv // self.batch_number
+        # (a diagnostics round of metrics="torch" keeps the torch gathers: its records hold minibatch tensors across minibatches)
+        torch_records = diagnostics and self.metrics == "torch"
+        batches = (seams.NativeBatches if self._replay is not None and not torch_records else seams.TorchBatches)(self, W, td)
+        if not diagnostics:
+            watcher = seams.Unobserved(self)
+        elif torch_records:
+            watcher = seams.TorchObserver(self, batches, dr)
+        else:
+            watcher = seams.NativeObserver(self, batches, dr, self._native_metrics(bs))
+        critic, actor = self.critic_learner, self.actor_learner
         closs = aloss = torch.zeros((), device=self.device)
-        # buffer="native": ONE gather per minibatch b fills output set b % 2 of the replay (states, obs, actions, masks, td), issued right
-        # before critic_learner.backward(b); the critic side (states, actions, td) and the actor side (obs, actions, masks) of minibatch b
-        # are views of that set.  Why two alternating sets are enough: set b % 2 is next written by the gather of minibatch b + 2 (or of a
-        # later data pass).  The readers of minibatch b are critic.backward(b) (its saved tensors are released inside the call),
-        # critic.apply() of b (the post-step Q of the same states; the learner drops its reference there) and actor.backward(b).  In the
-        # loop below all three are issued -- on the one stream everything here runs on -- before the gather of b + 1, hence before that of
-        # b + 2: actor.backward(b) comes first in iteration b, then gather(b + 1), critic.backward(b + 1) and the two apply() calls, none of
-        # which reads minibatch b.  The second set is what keeps minibatch b intact while b + 1 is being gathered and used beside it.
-        # A diagnostics round of metrics="torch" keeps the torch gathers for the whole round: its records hold minibatch tensors across
-        # minibatches.  metrics="native" keeps nothing (the learners hand each minibatch's arrays to the accumulator when they have them).
-        watch = diagnostics and self.metrics == "native"
-        diagnostics = diagnostics and not watch
-        native = self._replay is not None and not diagnostics
-        sink = self._native_metrics(bs) if watch else None
-        cur = [None, None]
-
-        def critic_batch(b):
-            if native:
-                cur[b % 2] = self._replay.minibatch(idx[b], b % 2)
-                return cur[b % 2][0], cur[b % 2][2], cur[b % 2][4]
-            return states[idx[b]], actions[idx[b]], td[idx[b]]
-
-        def actor_batch(b):
-            if native:
-                return cur[b % 2][1], cur[b % 2][2], cur[b % 2][3]
-            return obs[idx[b]], actions[idx[b]], masks[idx[b]]
-
         for data_pass in range(self.data_passes):
-            if self._shuffle is not None:
-                perm = self._shuffle.permutation(data_pass, nv, round0 if eager else None)
-            else:
-                perm = torch.randperm(nv, device=self.device) if eager else perms[data_pass]
-            if flying is not None:
-                perm = flying[perm]
+            perm = self._order.order(data_pass, nv, perms)
             if eager:
-                self.critic_learner.update_target_network(self.train_step, data_pass)
-            collect = diagnostics and data_pass == 0
-            observe = watch and data_pass == 0
-            last = self.batch_number - 1
-
-            def observe_critic(b):
-                # the discounted returns of minibatch b into the accumulator's own buffer (buffer="native": one more gather launch)
-                if self._replay is not None:
-                    disc = self._replay.gather_values(dr, idx[b], sink.disc[b])
-                else:
-                    disc = sink.disc[b].copy_(dr[idx[b]])
-                self.critic_learner.observe = (sink, b, disc)
-            self.critic_learner.collect = self.actor_learner.collect = collect
-            crit_rec, act_rec = [], []
+                critic.update_target_network(self.train_step, data_pass)
+            batches.begin_pass(perm, bs, self.batch_number)
+            seen = watcher.begin_pass(data_pass)
+            unchecked = eager and not self._grads_checked   # once: no gradient of the attached nets lives outside the reduced buffer
             # Reference order (critic/learner.py:58-105, actor/learner.py:36-101): all critic minibatches, each followed by
             # the post-step Q of ITS minibatch, then all actor minibatches with those Q.  Neither net's step feeds the
             # other's, so interleaving them -- actor(b) right after critic(b) -- computes the same numbers; it lets the
             # gradient exchange of actor(b) and critic(b+1) share one all-reduce (B+1 collectives per pass, not 2B).
-            idx = [perm[b * bs:(b + 1) * bs] for b in range(self.batch_number)]
-            closs = self.critic_learner.backward(*critic_batch(0))
-            if not self._grads_checked and eager:   # once: no gradient of the attached nets lives outside the reduced buffer
+            closs = critic.backward(*batches.critic(0))
+            if unchecked:
                 self.reducer.check_covered()
             self.reducer(self.critic)
-            if observe:
-                observe_critic(0)
-                if last == 0:
-                    sink.grad_l1(0, [p.grad for p in optim_native.used_parameters(self.critic)])
-            q_b = self.critic_learner.apply()
+            seen.critic_reduced(0)
+            q_b = critic.apply()
+            seen.critic_applied(0)
             for b in range(self.batch_number):
-                if collect:
-                    crit_rec.append(dict(self.critic_learner.last, discounted=dr[idx[b]]))
-                if observe:
-                    self.actor_learner.observe = (sink, b)
-                aloss, _ = self.actor_learner.backward(*actor_batch(b), q_b, eps)
-                if collect:
-                    act_rec.append(self.actor_learner.last)
-                if not self._grads_checked and eager:
+                seen.before_actor(b)
+                aloss, _ = actor.backward(*batches.actor(b), q_b, eps)
+                seen.after_actor(b)
+                if unchecked and b == 0:
                     self.reducer.check_covered()
                     self._grads_checked = True
                 if b + 1 < self.batch_number:
-                    closs = self.critic_learner.backward(*critic_batch(b + 1))
+                    closs = critic.backward(*batches.critic(b + 1))
                     self.reducer(self.critic, self.actor)
-                    if observe:
-                        observe_critic(b + 1)
-                        if b + 1 == last:     # the gradient figures are the last minibatch's, after the all-reduce, before the step clears them
-                            sink.grad_l1(0, [p.grad for p in optim_native.used_parameters(self.critic)])
-                    self.actor_learner.apply()
-                    q_b = self.critic_learner.apply()
+                    seen.critic_reduced(b + 1)
+                    seen.actor_reduced(b)
+                    actor.apply()
+                    q_b = critic.apply()
+                    seen.critic_applied(b + 1)
                 else:
                     self.reducer(self.actor)
-                    if observe:
-                        sink.grad_l1(1, [p.grad for p in optim_native.used_parameters(self.actor)])
-                    self.actor_learner.apply()
-            if observe:
-                # the KL figure: the updated actor on the pass's minibatches, through the configured no-grad path, then the closing launch
-                self.critic_learner.observe = self.actor_learner.observe = None
-                for b in range(self.batch_number):
-                    sink.actor_after(b, self._act_rows(obs[idx[b]], eps))
-                sink.finalize()
-            if collect:
-                from . import metrics
-                with torch.no_grad():
-                    after = [self.actor(obs[perm[b * bs:(b + 1) * bs]], eps)[0] for b in range(self.batch_number)]
-                self.last_diagnostics = dict(metrics.critic_metrics(crit_rec, self.critic))
-                self.last_diagnostics.update(metrics.actor_metrics(act_rec, self.actor, after))
-                self.critic_learner.collect = self.actor_learner.collect = False
+                    seen.actor_reduced(b)
+                    actor.apply()
+            seen.end_pass(eps)
             if data_pass == 0 and eager:
                 self.train_step += 1
         self.refresh_actor_inference()   # (recorded with the round when capture_graphs records it)
@@ -671,6 +556,23 @@ class COMATrainer:
                      _ffi.ptr(sums), _ffi.ptr(reward), self.E, env.stream)
         return glob
 
+    def _fly(self, t: int, policy: str, eps, actions=None, features: bool = False, observed=None) -> torch.Tensor:
+        """Step ``t`` of all envs under a named policy -> the step's reward [E,2]: "actor" (the current actor, greedy), "ig" (the greedy
+        expected-information-gain planner), "random" (uniform over the valid actions) or "explicit" (``actions`` int [E,N]).
+        ``observed`` is called between the observations and the move; ``features``: whether the move builds the critic's state."""
+        env = self.env
+        obs = env.build_observations(t, features=policy == "actor")
+        if observed is not None:
+            observed()
+        if policy == "actor":
+            probs = self._act(obs, eps)
+            return env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(self.E, self.N, self.A), features=features)[0]
+        if policy == "random":
+            return env.steps(t, policy=POLICY_UNIFORM, features=features)[0]
+        if policy == "ig":
+            actions = env.ig_actions(communication=True)
+        return env.steps(t, policy=POLICY_EXPLICIT, actions=actions, features=features)[0]
+
     def evaluate(self, waves: int = 1, counts_log: Optional[list] = None) -> Dict[str, object]:
         """Greedy (argmax) deployment of the current actor, the reference's coma_test loop for E envs at once: mean return and
         the per-step curves of target entropy and F1.  Index 0 = the prior map, index t+1 = the map holding every
@@ -692,9 +594,7 @@ class COMATrainer:
             ret = torch.zeros(self.E, device=self.device)
             team_ret = torch.zeros(self.E, device=self.device)
             for t in range(self.T):
-                obs = env.build_observations(t)
-                probs = self._act(obs, self.eps)
-                reward, _, _ = env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(self.E, self.N, self.A))
+                reward = self._fly(t, "actor", self.eps, features=True)
                 team_ret += reward[:, 0]
                 ret += (self.last_agent_reward() if self.deepq else reward)[:, 0]
                 pending = self.global_map_with_pending()
@@ -721,7 +621,6 @@ class COMATrainer:
         Does not touch the training buffer, the wave counter or epsilon.
         -> mean relative return ("episode_return": what COMA's reward is made of, utils/reward.py:25-40), mean absolute return, and
         the final global maps' mean target-region entropy and F1."""
-        from .vec_env import POLICY_EXPLICIT, POLICY_UNIFORM
         if policy not in ("actor", "random", "ig"):
             raise ValueError(f"unknown policy {policy!r}")
         env = self.env
@@ -729,16 +628,7 @@ class COMATrainer:
         ret = torch.zeros(self.E, device=self.device)
         abs_ret = torch.zeros(self.E, device=self.device)
         for t in range(self.T):
-            if policy == "actor":
-                obs = env.build_observations(t)
-                probs = self._act(obs, self.eps_dev if self.graphs else self.eps)
-                reward, _, _ = env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(self.E, self.N, self.A), features=False)
-            elif policy == "ig":
-                env.build_observations(t, features=False)
-                reward, _, _ = env.steps(t, policy=POLICY_EXPLICIT, actions=env.ig_actions(communication=True), features=False)
-            else:
-                env.build_observations(t, features=False)
-                reward, _, _ = env.steps(t, policy=POLICY_UNIFORM, features=False)
+            reward = self._fly(t, policy, self.eps_dev if self.graphs else self.eps)
             ret += reward[:, 0]
             abs_ret += reward[:, 1]
         ent, f1 = self.map_metrics(self.global_map_with_pending())
@@ -757,7 +647,6 @@ class COMATrainer:
         right after build_observations(t) has launched step t's fusion -- it is scored there (VecEnv.score_maps), before steps(t) --
         and only the last index needs the pending measurements fused into a copy (global_map_with_pending).  One host
         synchronisation, at the end."""
-        from .vec_env import POLICY_EXPLICIT, POLICY_UNIFORM
         if policy not in ("actor", "random", "ig", "explicit"):
             raise ValueError(f"unknown policy {policy!r}")
         env, T, E, N = self.env, self.T, self.E, self.N
@@ -772,18 +661,9 @@ class COMATrainer:
         flown = torch.empty(T, E, N, dtype=torch.int32, device=self.device)
         scores = [env.score_maps()]            # the prior map
         for t in range(T):
-            obs = env.build_observations(t, features=policy == "actor")
-            if t > 0:
-                scores.append(env.score_maps())
-            if policy == "actor":
-                probs = self._act(obs, self.eps_dev if self.graphs else self.eps)
-                reward, _, _ = env.steps(t, policy=POLICY_ARGMAX, probs=probs.view(E, N, self.A), features=False)
-            elif policy == "ig":
-                reward, _, _ = env.steps(t, policy=POLICY_EXPLICIT, actions=env.ig_actions(communication=True), features=False)
-            elif policy == "explicit":
-                reward, _, _ = env.steps(t, policy=POLICY_EXPLICIT, actions=actions[t], features=False)
-            else:
-                reward, _, _ = env.steps(t, policy=POLICY_UNIFORM, features=False)
+            # (the map of index t is scored between step t's fusion launch and its move)
+            reward = self._fly(t, policy, self.eps_dev if self.graphs else self.eps, actions=None if actions is None else actions[t],
+                               observed=(lambda: scores.append(env.score_maps())) if t > 0 else None)
             ret += reward[:, 0]
             abs_ret += reward[:, 1]
             faults |= env.fault
@@ -802,8 +682,7 @@ class COMATrainer:
 
     # ---- trainer state: stop a run between two rounds, continue it bit for bit ------------------------------------------------------------
     STATE_FORMAT = 1
-    SWITCHES = ("rollout_log", "metrics", "buffer", "actor_inference", "critic_inference", "adam", "head_update", "conv2_update",
-                "trunk_update", "shuffle")
+    SWITCHES = tuple(switches.TABLE)
 
     def _state_modules(self):
         return {"actor": self.actor, "critic": self.critic, "target_critic": self.critic_learner.target_critic,
@@ -871,10 +750,7 @@ class COMATrainer:
         self.eval_wave, self.step_replays = int(c["eval_wave"]), int(c["step_replays"])
         self.eps = float(c["eps"])
         self.eps_dev.fill_(self.eps)
-        if self._shuffle is not None:
-            self._shuffle.set_round(int(c["shuffle_round"]))
-        if self.shuffle == "torch" and state.get("rng") is not None:     # (the process-wide generator: only for who draws from it)
-            torch.cuda.set_rng_state(state["rng"].to("cpu", torch.uint8), self.device)
+        self._order.load(c, state.get("rng"))
         if self._native is not None and self._native.module is self.actor:
             self._native.sync()
         if self.critic_inference == "native":
