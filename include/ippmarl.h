@@ -155,7 +155,7 @@ int ippm_read_counters(ippm_ctx* ctx, ippm_counters* out, int reset, void* strea
 #define IPPM_T_ACTOR_FEAT 3   /* K6 actor */
 #define IPPM_T_CRITIC_FEAT 4  /* K6 critic */
 #define IPPM_T_RESET 5        /* reset: scalars, truth split, prior fills */
-#define IPPM_T_TERRAIN 6      /* random-field synthesis passes */
+#define IPPM_T_TERRAIN 6      /* random-field synthesis passes, the terrain library's draw */
 #define IPPM_T_RESET_MAPS 7   /* ippm_reset_maps: box-limited prior fill + start-position sensing */
 #define IPPM_T_AGENT_REWARD 8 /* ippm_agent_rewards: k_agent_rewards */
 #define IPPM_TIMED_CLASSES 9
@@ -821,6 +821,39 @@ int ippm_terrain_pack(ippm_ctx* ctx, const float* field, const uint32_t* range_k
 int ippm_terrain_truth(ippm_ctx* ctx, const int64_t* episode, const float* amp, float* work, uint32_t* range_keys, uint8_t* truth,
                        int32_t n_envs, void* stream);
 
+/* ---- terrain library: episodes over caller-supplied ground-truth maps ------------------------------------------------------------------
+ * The caller hands over n_maps binary maps of lgx x lgy cells once; they are kept bit-packed on the device, and every reset cuts each
+ * env's truth plane out of them: a map, a crop window of the grid's size and, optionally, one of the 8 symmetries of the square, drawn
+ * from (philox_seed, episode) alone -- fixed episodes mean the same truth in every batch, on every rank, whoever flies them.
+ *   THE DRAW of episode ep under seed s:
+ *     r = Philox4x32-10(counter = (0, ep & 0xFFFFFFFF, stream word(agent 0, stage 0, domain 5), ep >> 32), key = (s & 0xFFFFFFFF, s >> 32))
+ *     (the counter convention of the action and comm draws; domain 5 is this draw's own); mulhi(w, n) = (uint64) w * n >> 32.
+ *     sym  bit 0 (flip x) and bit 1 (flip y) = r[3] & 3 when flags & IPPM_LIBRARY_FLIP, else 0;
+ *          bit 2 (transpose) = (r[3] >> 2) & 1 when flags & IPPM_LIBRARY_TRANSPOSE, else 0.
+ *     m    = mulhi(r[0], n_maps).
+ *     The window has wr x wc library cells, (gx, gy) untransposed, (gy, gx) transposed:
+ *     x0 = mulhi(r[1], lgx - wr + 1), y0 = mulhi(r[2], lgy - wc + 1).
+ *     truth(x, y) = L_m[u][v] with x' = (sym & 1) ? gx - 1 - x : x, y' = (sym & 2) ? gy - 1 - y : y and
+ *     (u, v) = (x0 + x', y0 + y') untransposed, (x0 + y', y0 + x') transposed.
+ *   Sizes, checked on the host before any launch (-1 with ippm_last_error set, nothing launched): n_maps >= 1, lgx >= gx and lgy >= gy;
+ *   with IPPM_LIBRARY_TRANSPOSE also lgx >= gy and lgy >= gx; one packed map stays below 2^31 bytes; flags has no other bits.
+ *   LAYOUT of the packed library (a C caller may pack on the host): uint32 words, map m, row u starts at word (m * lgx + u) * lw with
+ *   lw = ceil(lgy / 32); cell v of the row is bit v & 31 of word v >> 5; bits past lgy are zero.  ippm_terrain_library_bytes =
+ *   n_maps * lgx * lw * 4: no tail padding -- the draw reads single words through a bounds-checked buffer resource of the drawn map.
+ * ippm_terrain_library_pack: cells uint8 [n_maps, lgx, lgy] on the device, nonzero = target class -> lib.  One launch, every byte of lib
+ *   is written; needs no context.
+ * ippm_terrain_library_draw: one launch (timed under IPPM_T_TERRAIN) writes, for every env, ALL ippm truth bytes of its plane (the
+ *   row-major bit string of the truth layout above whatever the maps' storage layout; the padding bits behind the last cell and the spare
+ *   byte of grids with gy % 4 != 0 are written as zero) and, when draws is given, draws int32 [E,4] = (m, x0, y0, sym).  Grid and seed are
+ *   the context's.  No atomics, no scratch, no allocation, no synchronisation; launches on `stream` only and can be captured.  Any
+ *   n_envs >= 1 whose workgroups (n_envs * ceil(truth words / 256), or n_envs * ceil(gx / 32) when transposing) stay below 2^31. */
+#define IPPM_LIBRARY_FLIP 1
+#define IPPM_LIBRARY_TRANSPOSE 2
+int ippm_terrain_library_bytes(int32_t n_maps, int32_t lgx, int32_t lgy, int64_t* bytes);
+int ippm_terrain_library_pack(const uint8_t* cells, int32_t n_maps, int32_t lgx, int32_t lgy, uint32_t* lib, void* stream);
+int ippm_terrain_library_draw(ippm_ctx* ctx, const int64_t* episode, const uint32_t* lib, int32_t n_maps, int32_t lgx, int32_t lgy,
+                              int32_t flags, int32_t* draws, uint8_t* truth, int32_t n_envs, void* stream);
+
 /* Host helpers (no GPU needed): exported so that CPU-only tests can pin the device's integer streams and
  * resize weights to NumPy / the oracle. */
 int ippm_area_weights(int32_t n_src, int32_t n_dst, int32_t* bin0, float* w0, float* w1);
@@ -828,6 +861,9 @@ int ippm_host_philox(const uint32_t* ctr_key6, uint32_t* out4);           /* Phi
 int ippm_host_start_state(int32_t env_seed, int64_t episode, int32_t agent, int32_t spacing, int32_t space_x,
                           int32_t space_y, int32_t* out3);                /* state_space.py:28-51 */
 int ippm_host_truth_params(int64_t episode, int32_t* out2);               /* ground_truths.py:43-48 */
+/* the draw of ippm_terrain_library_draw for one episode: out4 = (m, x0, y0, sym); the same size checks and error returns */
+int ippm_host_library_draw(uint64_t seed, int64_t episode, int32_t n_maps, int32_t lgx, int32_t lgy, int32_t gx, int32_t gy,
+                           int32_t flags, int32_t* out4);
 
 #ifdef __cplusplus
 }

@@ -328,6 +328,7 @@ __host__ __device__ __forceinline__ Philox4 ippm_philox(uint32_t c0, uint32_t c1
 #define IPPM_DOMAIN_ACTION 1u
 #define IPPM_DOMAIN_COMM 2u
 #define IPPM_DOMAIN_SHUFFLE 4u   // (3: the terrain's, terrain.hip) the minibatch permutation's round functions, shuffle.hip
+#define IPPM_DOMAIN_LIBRARY 5u   // an episode's map, window and symmetry out of a terrain library, terrain_library.hip
 __host__ __device__ __forceinline__ uint32_t ippm_stream_word(uint32_t agent, uint32_t stage, uint32_t domain) {
   return (agent & 0xFFu) | ((stage & 0xFFFFu) << 8) | ((domain & 0xFFu) << 24);
 }

@@ -151,10 +151,14 @@ PROTOTYPES = {
     "ippm_terrain_field": [P, P, P, P, P, P, P, I32, P],
     "ippm_terrain_pack": [P, P, P, P, I32, P],
     "ippm_terrain_truth": [P, P, P, P, P, P, I32, P],
+    "ippm_terrain_library_bytes": [I32, I32, I32, P],
+    "ippm_terrain_library_pack": [P, I32, I32, I32, P, P],
+    "ippm_terrain_library_draw": [P, P, P, I32, I32, I32, I32, P, P, I32, P],
     "ippm_area_weights": [I32, I32, P, P, P],
     "ippm_host_philox": [P, P],
     "ippm_host_start_state": [I32, I64, I32, I32, I32, I32, P],
     "ippm_host_truth_params": [I64, P],
+    "ippm_host_library_draw": [C.c_uint64, I64, I32, I32, I32, I32, I32, I32, P],
 }
 
 _lib: Optional[C.CDLL] = None
@@ -306,6 +310,17 @@ def host_truth_params(episode):
     out = (C.c_int32 * 2)()
     check(lib.ippm_host_truth_params(episode, out), "ippm_host_truth_params")
     return int(out[0]), int(out[1])
+
+
+LIBRARY_FLIP, LIBRARY_TRANSPOSE = 1, 2   # IPPM_LIBRARY_* flags of the terrain library's draw
+
+
+def host_library_draw(seed, episode, n_maps, lgx, lgy, gx, gy, flags):
+    """(m, x0, y0, sym) of ippm_terrain_library_draw for one episode (ippm_host_library_draw)."""
+    lib = load_library()
+    out = (C.c_int32 * 4)()
+    check(lib.ippm_host_library_draw(seed & 0xFFFFFFFFFFFFFFFF, episode, n_maps, lgx, lgy, gx, gy, flags, out), "ippm_host_library_draw")
+    return tuple(int(v) for v in out)
 
 
 def host_area_weights(n_src, n_dst=FEAT):

@@ -14,6 +14,9 @@ field's min / max and for its threshold bits, or (128 / 256 cells a side, 128 en
 that keeps the rows in registers, so that the field is never stored (``ippm_terrain_truth``;
 ``ippm_terrain_field`` + ``ippm_terrain_pack`` are the same arithmetic with the field written out); other grid sizes
 (the default 493 x 493) use ``ippm_terrain_noise`` + rocFFT via torch.fft and ``ippm_terrain_pack``.
+
+``terrain="library"`` (``LibraryTerrain``, at the end of this module) flies over the caller's own maps instead: crops of a device-resident
+library, drawn per episode (csrc/terrain_library.hip).
 """
 from typing import Optional
 
@@ -83,3 +86,71 @@ class RandomFieldTerrain:
                 field = torch.fft.ifft2(torch.fft.fft2(noise) * self.amp).real
             field = field.contiguous()
             self.ctx.call("ippm_terrain_pack", _ffi.ptr(field), None, _ffi.ptr(tr), n, stream)
+
+
+# ---- terrain library: episodes over caller-supplied ground-truth maps ------------------------------------------------------------------
+AUGMENT_FLAGS = {"none": 0, "flips": _ffi.LIBRARY_FLIP, "d4": _ffi.LIBRARY_FLIP | _ffi.LIBRARY_TRANSPOSE}
+
+
+def load_library(path: str) -> np.ndarray:
+    """Maps of a ``.npy`` file (one ``[M, lgx, lgy]`` array, or one ``[lgx, lgy]`` map) or of an ``.npz`` archive (every array of it, in the
+    archive's order, each one map or a stack of maps of one shape) as uint8 ``[M, lgx, lgy]``, nonzero = target class."""
+    data = np.load(path, allow_pickle=False)
+    if isinstance(data, np.ndarray):
+        return _as_maps(data)
+    with data:
+        return _as_maps([data[k] for k in data.files])
+
+
+def _as_maps(maps) -> np.ndarray:
+    """uint8 [M, lgx, lgy] (1 = target class) of an array, a tensor or a list of equally shaped ones (2-D: one map, 3-D: a stack)."""
+    if isinstance(maps, (list, tuple)):
+        parts = [np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m) for m in maps]
+        if not parts:
+            raise ValueError("terrain library: no maps")
+        parts = [p[None] if p.ndim == 2 else p for p in parts]
+        if any(p.ndim != 3 or p.shape[1:] != parts[0].shape[1:] for p in parts):
+            raise ValueError("terrain library: the maps must be 2-D and of one shape")
+        arr = np.concatenate(parts, axis=0)
+    else:
+        arr = np.asarray(maps.cpu() if isinstance(maps, torch.Tensor) else maps)
+        if arr.ndim == 2:
+            arr = arr[None]
+    if arr.ndim != 3 or 0 in arr.shape:
+        raise ValueError(f"terrain library: maps of shape [M, lgx, lgy] expected, not {arr.shape}")
+    return np.ascontiguousarray(arr != 0).astype(np.uint8)
+
+
+class LibraryTerrain:
+    """Ground truth cut out of a library of binary maps (csrc/terrain_library.hip): at every reset env e gets map ``m``, the window at
+    ``(x0, y0)`` and symmetry ``sym`` drawn from (philox_seed, episode[e]) -- the draw stated in include/ippmarl.h -- in one launch.
+    ``maps``: ``[M, lgx, lgy]`` bool / uint8 array or tensor, or a list of equally shaped maps; uploaded and bit-packed once.
+    ``augment``: "none" (crop only), "flips" (+ the two mirror images), "d4" (+ the transpose: all 8 symmetries of the square; the maps
+    must then hold the turned grid too).  ``draws``: device int32 [E,4] = (m, x0, y0, sym) of the last ``generate``."""
+
+    def __init__(self, derived, ctx: "_ffi.Context", device: torch.device, maps, augment: str = "d4"):
+        if augment not in AUGMENT_FLAGS:
+            raise ValueError(f"library_augment: 'none', 'flips' or 'd4', not {augment!r}")
+        self.d, self.ctx, self.device = derived, ctx, device
+        self.augment, self.flags = augment, AUGMENT_FLAGS[augment]
+        cells = _as_maps(maps)
+        self.n_maps, self.lgx, self.lgy = (int(v) for v in cells.shape)
+        # the size requirements are the library's (ippm_host_library_draw runs the checks of the draw itself): an IppmError here, not at the first reset
+        _ffi.host_library_draw(derived.philox_seed, 0, self.n_maps, self.lgx, self.lgy, derived.grid_x, derived.grid_y, self.flags)
+        nbytes = np.zeros(1, dtype=np.int64)
+        _ffi.check(ctx.lib.ippm_terrain_library_bytes(self.n_maps, self.lgx, self.lgy, nbytes.ctypes.data), "ippm_terrain_library_bytes")
+        self.lib = torch.empty(int(nbytes[0]) // 4, dtype=torch.int32, device=device)
+        dev_cells = torch.from_numpy(cells).to(device)
+        stream = torch.cuda.current_stream(device)
+        _ffi.check(ctx.lib.ippm_terrain_library_pack(_ffi.ptr(dev_cells), self.n_maps, self.lgx, self.lgy, _ffi.ptr(self.lib), stream.cuda_stream),
+                   "ippm_terrain_library_pack")
+        dev_cells.record_stream(stream)
+        self.draws: Optional[torch.Tensor] = None
+
+    def generate(self, episode: torch.Tensor, truth: torch.Tensor, stream: int) -> None:
+        """Writes the packed truth of ``episode[e]`` into ``truth[e]`` (both device tensors) and the draws into ``draws``."""
+        E = episode.numel()
+        if self.draws is None or self.draws.shape[0] != E:
+            self.draws = torch.zeros(E, 4, dtype=torch.int32, device=self.device)
+        self.ctx.call("ippm_terrain_library_draw", _ffi.ptr(episode), _ffi.ptr(self.lib), self.n_maps, self.lgx, self.lgy, self.flags,
+                      _ffi.ptr(self.draws), _ffi.ptr(truth), E, stream)

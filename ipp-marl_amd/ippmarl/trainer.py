@@ -32,6 +32,7 @@ class COMATrainer:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, waves_per_update: int = 1,
                  quirks: str = "reference", rank: int = 0, world: int = 1, first_episode: int = 1,
                  terrain: str = "split", graphs: bool = False, placement_draws: int = 0, team_sizes=None,
+                 terrain_library=None, library_augment: str = "d4",
                  shuffle: Optional[str] = None, rollout_log: Optional[str] = None, metrics: Optional[str] = None,
                  buffer: Optional[str] = None,
                  actor_inference: Optional[str] = None, critic_inference: Optional[str] = None, adam: Optional[str] = None,
@@ -57,7 +58,10 @@ class COMATrainer:
         self.eval_wave = 0                # the native log's slot of the next eval wave; read_rollout_log("eval", ...) rewinds it
         self.step_replays = 0             # recorded rollout steps replayed so far
         # team_sizes: mixed team sizes in one batch (VecEnv): the transitions of agents that do not fly never enter a minibatch
-        self.env = VecEnv(params, n_envs, device=device, philox_seed=philox_seed, terrain=terrain, team_sizes=team_sizes)
+        # terrain="library": every episode flies over a crop of `terrain_library` (VecEnv).  The library is not part of the trainer's state
+        # or fingerprint: a resumed run must be given the same maps and `library_augment` to fly the same episodes.
+        self.env = VecEnv(params, n_envs, device=device, philox_seed=philox_seed, terrain=terrain, team_sizes=team_sizes,
+                          terrain_library=terrain_library, library_augment=library_augment)
         # mission type DeepQ (coma_wrapper.py:113-171): every agent's transition carries ITS information gain (VecEnv.agent_reward, on
         # for DeepQ), each (env, agent) TD chain is built from its own rewards, and the return is the last flying agent's, as the
         # reference's EpisodeGenerator sums it; team_return keeps the COMA team reward beside it

@@ -106,7 +106,7 @@ class MapScores(NamedTuple):
 class VecEnv:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, terrain: str = "split",
                  track_area: bool = True, team_sizes=None, map_layout: str = "auto", layout_envs: Optional[int] = None,
-                 agent_rewards: Optional[bool] = None):
+                 agent_rewards: Optional[bool] = None, terrain_library=None, library_augment: str = "d4"):
         if not torch.cuda.is_available():
             raise _ffi.IppmError("VecEnv needs an AMD GPU (HIP): there is no CPU path for the env step")
         self.params = params
@@ -221,11 +221,19 @@ class VecEnv:
         self.state = None
         self.t = 0
         # "split": the half-plane truth the reference flies over (ground_truths.py:42-56); "random_field": the
-        # power-law random field it synthesises first (ground_truths.py:25-40), generated on the device (terrain.py)
-        if terrain not in ("split", "random_field"):
+        # power-law random field it synthesises first (ground_truths.py:25-40), generated on the device (terrain.py); "library": crops
+        # of the caller's own maps (`terrain_library`: [M, lgx, lgy] binary maps, uploaded and bit-packed once; `library_augment`: "none",
+        # "flips" or "d4"), map, window and symmetry drawn per episode from (philox_seed, episode) on the device (terrain.LibraryTerrain)
+        if terrain not in ("split", "random_field", "library"):
             raise ValueError(f"unknown terrain {terrain!r}")
         self.terrain = terrain
         self._field = None
+        self._library = None
+        if terrain_library is not None:
+            from .terrain import LibraryTerrain
+            self._library = LibraryTerrain(self.d, self.ctx, self.device, terrain_library, library_augment)
+        elif terrain == "library":
+            raise ValueError('terrain="library" needs terrain_library (the maps to fly over)')
         self._pending_t = None   # step whose fusion (K4 + K5) build_observations has already launched
         self._boxes_valid = False  # ws holds, per map, the box of everything written since the last reset (kept by the plan kernel)
         self._profile = False    # time the kernels with events bound to their dispatches (bench.py's roofline legs)
@@ -326,7 +334,7 @@ class VecEnv:
     def reset(self, episodes, truth: Optional[torch.Tensor] = None, start_positions: Optional[torch.Tensor] = None,
               flips: Optional[torch.Tensor] = None, terrain: Optional[str] = None):
         """Starts episode ``episodes[e]`` in env e (all envs at once) and performs the t=0 start-position sensing.
-        ``truth`` (explicit [E,gx,gy] field) overrides ``terrain`` ("split" | "random_field", default: the env's)."""
+        ``truth`` (explicit [E,gx,gy] field) overrides ``terrain`` ("split" | "random_field" | "library", default: the env's)."""
         d = self.d
         terrain = self.terrain if terrain is None else terrain
         ep = torch.as_tensor(episodes, dtype=torch.int64).reshape(self.E)
@@ -363,6 +371,10 @@ class VecEnv:
                     torch.cuda.current_stream(self.device).wait_event(self._next_ready)
                 self._terrain().generate(self.episode, self.truth, self.stream)
             self._next_ids = None
+        elif terrain == "library":
+            if self._library is None:
+                raise ValueError('terrain="library" needs the env\'s terrain_library (the maps to fly over)')
+            self._library.generate(self.episode, self.truth, self.stream)
         elif terrain != "split":
             raise ValueError(f"unknown terrain {terrain!r}")
         if start_positions is not None:
@@ -377,6 +389,11 @@ class VecEnv:
             self._boxes_valid = True
         else:
             self._sense(stage=0, flips=flips)
+
+    @property
+    def library_draws(self) -> Optional[torch.Tensor]:
+        """Device int32 [E,4] = (map, x0, y0, sym) of the last reset over the terrain library (None before the first)."""
+        return None if self._library is None else self._library.draws
 
     def _terrain(self):
         if self._field is None:
@@ -781,7 +798,8 @@ class SplitVecEnv:
     through one actor batch and use ``VecEnv`` directly."""
 
     def __init__(self, params: Dict, n_envs: int, parts: int = 2, device: str = "cuda:0", philox_seed: int = 3, terrain: str = "split",
-                 track_area: bool = False, team_sizes=None, map_layout: str = "auto", agent_rewards: Optional[bool] = None):
+                 track_area: bool = False, team_sizes=None, map_layout: str = "auto", agent_rewards: Optional[bool] = None,
+                 terrain_library=None, library_augment: str = "d4"):
         if parts < 1 or n_envs < parts:
             raise ValueError("SplitVecEnv: 1 <= parts <= n_envs")
         self.device = torch.device(device)
@@ -794,11 +812,12 @@ class SplitVecEnv:
         self.stream_redraws, self.stream_probe = self._spread_streams()
         ts = None if team_sizes is None else [int(v) for v in team_sizes]
         self.parts = []
+        # (terrain_library: every part packs its own copy on its own stream -- 8 MB for 64 maps of 1024 x 1024)
         for k, (n, off) in enumerate(zip(self.sizes, self.offsets)):
             with torch.cuda.stream(self.streams[k]):
                 self.parts.append(VecEnv(params, n, device=device, philox_seed=philox_seed, terrain=terrain, track_area=track_area,
                                          team_sizes=None if ts is None else ts[off:off + n], map_layout=map_layout, layout_envs=int(n_envs),
-                                         agent_rewards=agent_rewards))
+                                         agent_rewards=agent_rewards, terrain_library=terrain_library, library_augment=library_augment))
         self.E = int(n_envs)
         self.d = self.parts[0].d
         self.tiled = self.parts[0].tiled
