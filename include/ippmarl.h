@@ -131,7 +131,7 @@ typedef struct ippm_counters {
   uint64_t fuse_global_ops;
   uint64_t feature_cells;      /* K6: map cells streamed by the feature builders */
   uint64_t reserved[2];        /* [0]: fusion launches that were handed a work list of the other form and skipped it (0 in a
-                                  correct call sequence) */
+                                  correct call sequence); [1]: cells whose value ippm_settle_clamps changed */
 } ippm_counters;
 
 const char* ippm_last_error(void);
@@ -295,6 +295,29 @@ int ippm_set_team_sizes(ippm_ctx* ctx, const int32_t* n_active);
  * reference (mapping/mappings.py:126-132 allocates fresh prior maps per episode). */
 int ippm_dirty_slab_words(ippm_ctx* ctx, int32_t n_envs, int64_t* words);
 int ippm_set_dirty_slabs(ippm_ctx* ctx, int32_t* slabs);
+/* Clamp backlog: the deferred clamp's clips, paid only when a map is read.  A plan that takes messages puts clamp-only
+ * ops ahead of its real ops (over the region the last fusion or left-behind footprints may have left out of range, and over the agent's
+ * last footprint); the cells of those that no real op meets are loaded, clipped and stored although nothing needs the clipped value in
+ * memory until somebody looks at the map: every later op and ippm_sense_step clip their input themselves, ippm_reset_maps discards the
+ * cells, and their reward terms are exact zeros.  With a registered backlog --
+ * backlog: DEVICE int32 [ippm_clamp_backlog_words(n_envs)], caller-owned, 16-byte aligned, ZEROED before the first use; per map the
+ * bounding box of the clips it is owed and the exact list of the rectangles written unclamped since its last fusion (budget + 2 entries:
+ * one footprint per step of an episode and the fusion's own rectangle) -- the planners keep that list, and ippm_plan_step with
+ * IPPM_STEP_DEFER_CLAMPS (tile form only; ignored elsewhere and without a backlog) pushes no clamp-only op: the rectangles join the
+ * owed box.  A plan step WITHOUT the flag pays everything owed as part of its own clamp ops (today's plans plus the box).
+ * ippm_settle_clamps (one launch, an early exit for maps that owe nothing) clips every cell of a map's owed box that is not legitimately
+ * unclamped at that moment, cell for cell what the undeferred plans would have left, and empties the box: call it before ANYTHING other
+ * than ippm_plan_step / ippm_fuse_step / ippm_sense_step / the resets reads or writes `local` / `global` (read-back, features, area sums,
+ * ippm_agent_rewards, scoring, the planners' candidate gains, captured graphs, ...).  Do not defer when area sums are tracked.  The resets
+ * (ippm_reset_episode, ippm_reset_maps) empty the backlog of the maps they reset.  The list holds an episode: a caller that steps a map more
+ * than budget + 1 times between resets settles and stops deferring at that point (past it the list overflows, plans fall back to the
+ * undeferred path by themselves, but a box still owed then can no longer be settled exactly).  `rect` = the published footprints
+ * (ippm_sense_step's), `ws` the workspace.  Cells changed by the settles are counted in ippm_counters.reserved[1].  NULL: no backlog (default). */
+#define IPPM_STEP_DEFER_CLAMPS 16
+int ippm_clamp_backlog_words(ippm_ctx* ctx, int32_t n_envs, int64_t* words);
+int ippm_set_clamp_backlog(ippm_ctx* ctx, int32_t* backlog);
+int ippm_settle_clamps(ippm_ctx* ctx, float* local, float* global, const int32_t* ws, const int32_t* rect, int32_t* backlog,
+                       int32_t n_envs, void* stream);
 /* Storage layout of the belief maps (`local`, `global` of every entry point of this context).  0 (the default): row-major, cell (x, y) at
  * float x * grid_y + y -- the reference's numpy layout (mapping/mappings.py:18-25).  1: TILE STORAGE -- 128-byte tiles of 4 rows x 8 cells, the
  * tiles in row-major order: cell (x, y) at float (x >> 2) * 4 grid_y + (y >> 3) * 32 + (x & 3) * 8 + (y & 7).  Same size, same values; every

@@ -16,13 +16,17 @@
 __global__ void k_reset_scalars(const ippm_config* __restrict__ c, const int64_t* __restrict__ episode,
                                 int32_t* __restrict__ pos, int32_t* __restrict__ split_pct,
                                 float* __restrict__ comm_range, int32_t* __restrict__ ws, double* __restrict__ sums,
-                                double* __restrict__ area, int n_envs) {
+                                double* __restrict__ area, int n_envs, int32_t* __restrict__ backlog, int bl_words) {
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int n = c->n_agents;
   int per = n + 1;
   if (tid >= n_envs * per) return;
   int e = tid / per, k = tid % per;
   int64_t ep = episode[e];
+  if (backlog) {   // the new episode owes no clip and has written nothing unclamped (ippm_set_clamp_backlog)
+    int32_t* bl = backlog + (size_t)(e * per + k) * bl_words;
+    bl[BL_OWED_X] = 0; bl[BL_OWED_Y] = 0; bl[BL_LEGIT_N] = 0;
+  }
   // clear this map's workspace (deferred clamp state + plan)
   int32_t* w = ws + (size_t)(e * per + k) * IPPM_WS_WORDS;
   // the written-cells box of the finished episode moves to the (now idle) first op record, where every workgroup of
@@ -504,7 +508,8 @@ __global__ void __launch_bounds__(256)
 k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ episode, const int32_t* __restrict__ pos,
              const uint8_t* __restrict__ truth, float* __restrict__ local, float* __restrict__ global, const uint8_t* __restrict__ flips,
              uint8_t* __restrict__ code, const int32_t* __restrict__ rect, int32_t* __restrict__ ws, int full, int fill_chunks,
-             const int32_t* __restrict__ n_active, int col_align, int32_t* __restrict__ slabs, int n_slabs, int tl) {
+             const int32_t* __restrict__ n_active, int col_align, int32_t* __restrict__ slabs, int n_slabs, int tl,
+             int32_t* __restrict__ backlog, int bl_words) {
   const int n = c->n_agents, gx = c->grid_x, gy = c->grid_y, S = c->tile_stride;
   const int e = blockIdx.z, m = blockIdx.y;
   const bool is_global = m == n;
@@ -540,6 +545,10 @@ k_reset_maps(const ippm_config* __restrict__ c, const int64_t* __restrict__ epis
     if (blockIdx.x == 0 && threadIdx.x == 0) {   // the new episode's box: what this launch writes that is not the prior
       w[WS_BBOX_X] = xl | (xr << 16);
       w[WS_BBOX_Y] = yu | (yd << 16);
+      if (backlog) {   // ... which owes no clip (the cells that did are filled or sensed anew here)
+        int32_t* bl = backlog + (size_t)(e * (n + 1) + m) * bl_words;
+        bl[BL_OWED_X] = 0; bl[BL_OWED_Y] = 0; bl[BL_LEGIT_N] = 0;
+      }
     }
     if (slabs) {
       // Dirty slabs (ippm_set_dirty_slabs): instead of the map's one box, every 16-row slab has its own column interval -- what the
@@ -748,7 +757,7 @@ extern "C" int ippm_reset_episode(ippm_ctx* ctx, const int64_t* episode, int32_t
   const ippm_config& c = ctx->cfg;
   const int per = c.n_agents + 1;
   IPPM_LAUNCH(ctx, IPPM_T_RESET, k_reset_scalars, dim3(grid1((size_t)n_envs * per, 64)), dim3(64), S_(stream), ctx->dcfg, episode, pos,
-                     split_pct, comm_range_out, ws, sums, area, n_envs);
+                     split_pct, comm_range_out, ws, sums, area, n_envs, ctx->backlog, ippm_backlog_words(ctx));
   IPPM_LAUNCH_CHECK("reset_scalars");
   const size_t cells = (size_t)c.grid_x * c.grid_y;
   if (truth) {
@@ -780,7 +789,8 @@ extern "C" int ippm_reset_maps(ippm_ctx* ctx, const int64_t* episode, const int3
   const int fill_chunks = (c.grid_x + IPPM_RESET_ROWS - 1) / IPPM_RESET_ROWS, sense_parts = ctx->tl ? ((h_max + 3) / 4 + 1 + 7) / 8 : (h_max + 31) / 32;
   dim3 grid((unsigned)(fill_chunks + sense_parts), (unsigned)(c.n_agents + 1), (unsigned)n_envs);
   IPPM_LAUNCH(ctx, IPPM_T_RESET_MAPS, k_reset_maps, grid, dim3(256), S_(stream), ctx->dcfg, episode, pos, truth, local, global, flips, code, rect,
-              ws, full ? 1 : 0, fill_chunks, ctx->n_active, (c.grid_y % 32 == 0 && !ctx->tl) ? 32 : 0, ctx->slabs, ippm_slab_count(ctx), ctx->tl);
+              ws, full ? 1 : 0, fill_chunks, ctx->n_active, (c.grid_y % 32 == 0 && !ctx->tl) ? 32 : 0, ctx->slabs, ippm_slab_count(ctx), ctx->tl,
+              ctx->backlog, ippm_backlog_words(ctx));
   IPPM_LAUNCH_CHECK("reset_maps");
   return 0;
 }

@@ -35,8 +35,16 @@
 // and re-armed slab by slab by ippm_reset_maps' FILL workgroups.
 #define IPPM_SLAB_ROWS 16
 #define IPPM_SLAB_EMPTY_LO 0x7FFFFFFF
+// ---- clamp backlog (ippm_set_clamp_backlog): int32 [E, N+1, BL_RECTS + 4 * cap], cap = budget + 2.  Per map: the clips it is OWED (DESIGN.md
+// "deferred clamp": a plan made with IPPM_STEP_DEFER_CLAMPS remembers the rectangles it would have clipped as ONE bounding box instead of
+// pushing clamp-only ops; ippm_settle_clamps pays) and the exact list of the rectangles written unclamped since the map's last fusion
+// (LEGIT: that fusion's last-op rectangle and the footprints K3 left behind while the agent heard nobody -- RECT_A holds only their hull).
+#define BL_OWED_X 0   // x0 | x1 << 16, BL_OWED_Y y0 | y1 << 16 (as WS_BBOX_*; x1 <= x0: nothing owed)
+#define BL_OWED_Y 1
+#define BL_LEGIT_N 2  // entries of the list; < 0: the list overflowed and is incomplete (plans then take the undeferred path)
+#define BL_RECTS 4    // entry k = words BL_RECTS + 4 k .. + 3 = [yu, yd, xl, xr]
 #define OP_WORDS 8
-#define OP_TYPE 0     // 0 = clamp only, 1 = fuse measurement
+#define OP_TYPE 0    // 0 = clamp only, 1 = fuse measurement
 #define OP_SRC 1      // source agent j of the measurement
 #define OP_LM0 2      // float bits: log-odds of the two measurement values at j's altitude (0 for a clamp-only op)
 #define OP_YU 3
@@ -66,6 +74,7 @@ struct ippm_ctx {
   // all derive from the context's settings and must agree for its lifetime)
   int knob_tile_rotate, knob_terrain_one_launch;
   int32_t* slabs = nullptr;    // ippm_set_dirty_slabs: per (env, map, 16-row slab) the column interval written since the episode's reset (device, caller-owned)
+  int32_t* backlog = nullptr;  // ippm_set_clamp_backlog: per map the owed clips and the rectangles written unclamped since its last fusion (device, caller-owned)
   const int32_t* n_active;   // device int32 [E] or nullptr: agents flying in each env (ippm_set_team_sizes)
   int k3_wpg, k3_chn, k3_go;        // workgroup shape of the env-only step's K3 (wavefronts per workgroup, loads in flight per lane)
   float2* d_roots;           // e^{2 pi i k / 1024}, k = 0..1023: the twiddle table of the terrain transforms (terrain.hip)
@@ -102,6 +111,8 @@ int ippm_work_env_cap(const ippm_ctx* ctx, int n_envs);    // items an env's sli
 // [E][cap] items of 4 words {run's first group | lane-loads << 16, first row, region's first group | groups per row << 16,
 // op mask | map slot << 24}, cap = ippm_tile_env_cap().
 int ippm_tile_env_cap(const ippm_ctx* ctx);
+static inline int ippm_backlog_cap(const ippm_ctx* ctx) { return ctx->cfg.budget + 2; }   // LEGIT entries per map: a footprint per step of an episode + the fusion's rectangle
+static inline int ippm_backlog_words(const ippm_ctx* ctx) { return BL_RECTS + 4 * ippm_backlog_cap(ctx); }   // words per map
 static inline int ippm_slab_count(const ippm_ctx* ctx) { return (ctx->cfg.grid_x + IPPM_SLAB_ROWS - 1) / IPPM_SLAB_ROWS; }   // dirty slabs per map
 int ippm_launch_fuse_tiles(ippm_ctx* ctx, float* local, float* global, const uint8_t* code, int32_t* ws, double* sums, double* area,
                            const int32_t* work, int n_envs, hipStream_t st);   // fuse_tiles.hip (area != nullptr: area sums tracked)

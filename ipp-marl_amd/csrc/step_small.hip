@@ -88,16 +88,36 @@ struct plan_src_lds {
 // n = the agents flying in this env (messages come from them only; strides use the configured team size), st = the map's first 6
 // workspace words (deferred-clamp state), prefetched by the caller; s_ops / s_nops = LDS mirror of the plan's rectangles and
 // their number for the tile builder (written when SRC::mirrors: a null test on a pointer into LDS is not free).
+// bl = the map's clamp backlog (ippm_set_clamp_backlog; nullptr: none), bl_cap = entries its LEGIT list holds.  With a backlog the footprints an agent
+// leaves behind while it hears nobody are listed one by one (RECT_A keeps only their hull).  `defer` (IPPM_STEP_DEFER_CLAMPS, tile form): a plan that takes
+// messages pushes NO clamp-only ops -- the rectangles it would have clipped join the backlog's OWED box, ippm_settle_clamps clips them when the map is read.
+// Every op clips its own input, K3 clips its input and the reset discards the cells: nothing else needs the clipped value in memory.
 template <class SRC>
 __device__ __forceinline__ int plan_map(const ippm_config* __restrict__ c, const SRC src, uint32_t recv, int32_t* __restrict__ ws,
-                                        int global_maps, int e, int i, const int32_t* st, int4* s_ops, int32_t* s_nops, int n) {
+                                        int global_maps, int e, int i, const int32_t* st, int4* s_ops, int32_t* s_nops, int n,
+                                        int32_t* __restrict__ bl = nullptr, int bl_cap = 0, bool defer = false, const int32_t* bh = nullptr) {
+  // (bh: the backlog's header words as the caller prefetched them beside `st`; without: read here)
+  const int bl_owed_x = bl ? (bh ? bh[BL_OWED_X] : bl[BL_OWED_X]) : 0, bl_owed_y = bl ? (bh ? bh[BL_OWED_Y] : bl[BL_OWED_Y]) : 0;
+  const int bl_n = bl ? (bh ? bh[BL_LEGIT_N] : bl[BL_LEGIT_N]) : 0;
   int32_t* w = ws + (size_t)(e * (c->n_agents + 1) + i) * IPPM_WS_WORDS;
   const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
   const uint32_t takes = global_maps ? all : (recv & ~(1u << i) & all);
   int32_t* hdr = w + WS_PLAN;
+  auto empty = [](int4 r) { return r.w <= r.z || r.y <= r.x; };   // r = {yu, yd, xl, xr}: an empty rectangle makes no op
   if (takes == 0) {  // nothing received: the map is untouched; carry possible out-of-range regions forward
     if (!global_maps && st[WS_FLAG_S]) {
       const int4 ri = src.rect(i);
+      if (bl && bl_n >= 0) {
+        // the exact rectangles behind the hull below.  An empty list with FLAG_A set: RECT_A still is the last fusion's last-op rectangle
+        int nl = bl_n;
+        int4* lr = reinterpret_cast<int4*>(bl + BL_RECTS);
+        if (nl == 0 && st[WS_FLAG_A]) lr[nl++] = make_int4(st[WS_RECT_A], st[WS_RECT_A + 1], st[WS_RECT_A + 2], st[WS_RECT_A + 3]);
+        if (!empty(ri)) {
+          if (nl < bl_cap) lr[nl++] = ri;
+          else nl = -1;   // (more steps than an episode has: the list is incomplete from here on)
+        }
+        bl[BL_LEGIT_N] = nl;
+      }
       if (st[WS_FLAG_A]) {
         w[WS_RECT_A + 0] = min(st[WS_RECT_A + 0], ri.x); w[WS_RECT_A + 1] = max(st[WS_RECT_A + 1], ri.y);
         w[WS_RECT_A + 2] = min(st[WS_RECT_A + 2], ri.z); w[WS_RECT_A + 3] = max(st[WS_RECT_A + 3], ri.w);
@@ -114,7 +134,6 @@ __device__ __forceinline__ int plan_map(const ippm_config* __restrict__ c, const
   const int last_src = 31 - __clz(takes);
   int nops = 0, x0 = 1 << 30, x1 = -1, y0 = 1 << 30, y1 = -1;
   int4* ops = reinterpret_cast<int4*>(w + WS_OPS);
-  auto empty = [](int4 r) { return r.w <= r.z || r.y <= r.x; };   // r = {yu, yd, xl, xr}: an empty rectangle makes no op
   auto push = [&](int4 r, int4 a, int4 b) {
     if (SRC::mirrors) s_ops[nops] = r;
     ops[nops * 2] = a;
@@ -125,8 +144,32 @@ __device__ __forceinline__ int plan_map(const ippm_config* __restrict__ c, const
   auto clamp_op = [&](int4 r) {   // an op that only clips (type 0)
     if (!empty(r)) push(r, make_int4(0, -1, 0, r.x), make_int4(r.y, r.z, r.w, 0));
   };
-  if (st[WS_FLAG_A]) clamp_op(make_int4(st[WS_RECT_A], st[WS_RECT_A + 1], st[WS_RECT_A + 2], st[WS_RECT_A + 3]));
-  if (!global_maps && st[WS_FLAG_S]) clamp_op(src.rect(i));
+  // what this fusion has to clip before its first real op: region A (the last fusion's last-op rectangle, or the hull of the footprints left
+  // behind since) and the agent's last footprint
+  int4 ca = st[WS_FLAG_A] ? make_int4(st[WS_RECT_A], st[WS_RECT_A + 1], st[WS_RECT_A + 2], st[WS_RECT_A + 3]) : make_int4(0, 0, 0, 0);
+  int4 cs = (!global_maps && st[WS_FLAG_S]) ? src.rect(i) : make_int4(0, 0, 0, 0);
+  if (bl) {
+    auto hull = [&](int4 a, int4 b) {
+      return empty(a) ? b : (empty(b) ? a : make_int4(min(a.x, b.x), max(a.y, b.y), min(a.z, b.z), max(a.w, b.w)));
+    };
+    // the clips owed so far: columns [o.x, o.y) x rows [o.z, o.w), like an op's rectangle
+    const int bx = bl_owed_x, by = bl_owed_y;
+    int4 o = make_int4(by & 0xFFFF, (unsigned)by >> 16, bx & 0xFFFF, (unsigned)bx >> 16);
+    if (defer && bl_n >= 0) {   // both join the owed box; no clamp-only op
+      o = hull(hull(o, ca), cs);
+      ca = cs = make_int4(0, 0, 0, 0);
+    } else {
+      // today's path pays everything, the owed box as part of region A's op (the plan stays within its op count; a fusion clips EVERY cell
+      // of its map in the reference, so the cells a hull adds are clipped rightly, and they were in range anyway)
+      ca = hull(ca, o);
+      o = make_int4(0, 0, 0, 0);
+    }
+    bl[BL_OWED_X] = o.z | (o.w << 16);
+    bl[BL_OWED_Y] = o.x | (o.y << 16);
+    bl[BL_LEGIT_N] = 0;   // a fusion follows: what was written unclamped before it is no longer
+  }
+  clamp_op(ca);
+  clamp_op(cs);
   int last_op = -1;
   for (uint32_t rem = takes; rem != 0; rem &= rem - 1u) {
     const int j = __ffs(rem) - 1;
@@ -154,7 +197,7 @@ __device__ __forceinline__ int plan_map(const ippm_config* __restrict__ c, const
 
 __global__ void k_plan(const ippm_config* __restrict__ c, const int32_t* __restrict__ rect,
                        const int32_t* __restrict__ pos, const uint8_t* __restrict__ comm, int32_t* __restrict__ ws,
-                       int global_maps, int n_envs, int agent_sel) {
+                       int global_maps, int n_envs, int agent_sel, int32_t* __restrict__ backlog, int bl_words) {
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = c->n_agents;
   const int per = (global_maps || agent_sel >= 0) ? 1 : n;
@@ -166,7 +209,8 @@ __global__ void k_plan(const ippm_config* __restrict__ c, const int32_t* __restr
     for (int j = 0; j < n; ++j) recv |= comm[(size_t)(e * n + i) * n + j] ? (1u << j) : 0u;
   int32_t st[6];
   for (int q = 0; q < 6; ++q) st[q] = ws[(size_t)(e * (n + 1) + i) * IPPM_WS_WORDS + q];
-  plan_map(c, plan_src_mem{c, rect + (size_t)e * n * 4, pos + (size_t)e * n * 3}, recv, ws, global_maps, e, i, st, nullptr, nullptr, n);
+  plan_map(c, plan_src_mem{c, rect + (size_t)e * n * 4, pos + (size_t)e * n * 3}, recv, ws, global_maps, e, i, st, nullptr, nullptr, n,
+           backlog ? backlog + (size_t)(e * (n + 1) + i) * bl_words : nullptr, (bl_words - BL_RECTS) >> 2, false);
 }
 
 // ======================================================================================================
@@ -350,7 +394,7 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
             const int32_t* __restrict__ action_in, uint8_t* __restrict__ mask, int32_t* __restrict__ action,
             int32_t* __restrict__ fault, int32_t* __restrict__ rect_next, int agent_sel, int32_t* __restrict__ work,
             int wave_rows, int env_cap, const int32_t* __restrict__ n_active,
-            int32_t* __restrict__ slabs, int n_slabs, int tile_round) {
+            int32_t* __restrict__ slabs, int n_slabs, int tile_round, int32_t* __restrict__ backlog, int bl_words) {
   // (argument order = latency order: what the first loads need -- positions, footprints, the maps' clamp state, the team size --
   // arrives in SGPRs with the wavefront, so the loads go out before anything else has been read)
   // Wavefront 0 plans (comm matrix, fusion plans, written-cells boxes).  With a tile-form work list the workgroup carries more
@@ -381,7 +425,7 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
   const int waves = (int)(blockDim.x >> 6);
   const int k1_wave = move ? (tiled && waves >= 3 ? 1 : 0) : -1;   // K1 beside the planning only when builders exist besides it
   int32_t* pg = pos + (size_t)e * n * 3;
-  int32_t st[6] = {0, 0, 0, 0, 0, 0};
+  int32_t st[6] = {0, 0, 0, 0, 0, 0}, bh[3] = {0, 0, 0};
   if (wv == 0) {
     // everything the workgroup will read is requested now, in one round trip: positions, published footprints, the
     // deferred-clamp state of my map (lane i: local map i, lane n: the global map)
@@ -394,6 +438,10 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
       const int4 a = wsm[0];
       const int2 b = *reinterpret_cast<const int2*>(wsm + 1);
       st[0] = a.x; st[1] = a.y; st[2] = a.z; st[3] = a.w; st[4] = b.x; st[5] = b.y;
+      if (backlog) {   // ... and its clamp backlog's header
+        const int4 h = *reinterpret_cast<const int4*>(backlog + (size_t)(e * (n + 1) + min(lane, n)) * bl_words);
+        bh[0] = h.x; bh[1] = h.y; bh[2] = h.z;
+      }
     }
     if (lane <= n) s_nops[lane] = 0;
     if (lane < n) s_recv[lane] = 0;
@@ -429,19 +477,22 @@ k_plan_step(int32_t* __restrict__ pos, const int32_t* __restrict__ rect, int32_t
       wave_sync_lds();
       if (lane < n) recv = s_recv[lane];
     }
+    int32_t* bl = backlog ? backlog + (size_t)(e * (n + 1) + min(lane, n)) * bl_words : nullptr;   // my map's clamp backlog
+    const int bl_cap = (bl_words - BL_RECTS) >> 2;
     if (tiled) {
       wave_sync_lds();
       const plan_src_lds src{s_rect4, s_rec};
+      const bool defer = (flags & IPPM_STEP_DEFER_CLAMPS) != 0;
       if ((flags & IPPM_STEP_COMM) && lane < na && (agent_sel < 0 || agent_sel == lane))
-        hull_rows = plan_map(c, src, recv, ws, 0, e, lane, st, s_ops + lane * IPPM_MAX_OPS, s_nops + lane, na);
+        hull_rows = plan_map(c, src, recv, ws, 0, e, lane, st, s_ops + lane * IPPM_MAX_OPS, s_nops + lane, na, bl, bl_cap, defer, bh);
       if ((flags & IPPM_STEP_GLOBAL) && lane == n)
-        hull_rows = plan_map(c, src, 0u, ws, 1, e, n, st, s_ops + n * IPPM_MAX_OPS, s_nops + n, na);
+        hull_rows = plan_map(c, src, 0u, ws, 1, e, n, st, s_ops + n * IPPM_MAX_OPS, s_nops + n, na, bl, bl_cap, defer, bh);
     } else {
       const plan_src_mem src{c, s_rect, s_pos};
       if ((flags & IPPM_STEP_COMM) && lane < na && (agent_sel < 0 || agent_sel == lane))
-        hull_rows = plan_map(c, src, recv, ws, 0, e, lane, st, nullptr, nullptr, na);
+        hull_rows = plan_map(c, src, recv, ws, 0, e, lane, st, nullptr, nullptr, na, bl, bl_cap, false, bh);
       if ((flags & IPPM_STEP_GLOBAL) && lane == n)
-        hull_rows = plan_map(c, src, 0u, ws, 1, e, n, st, nullptr, nullptr, na);
+        hull_rows = plan_map(c, src, 0u, ws, 1, e, n, st, nullptr, nullptr, na, bl, bl_cap, false, bh);
     }
     // an agent that does not fly (any more: team sizes may change between steps) gets an EMPTY plan, so that a fusion which
     // enumerates every map's plan from ws (no work list) never re-applies the plan it was left with when it last flew
@@ -547,7 +598,8 @@ int ippm_launch_plan(ippm_ctx* ctx, const int32_t* rect, const int32_t* pos, con
                      int n_envs, int agent_sel, hipStream_t st) {
   const int maps = (global_maps || agent_sel >= 0) ? n_envs : n_envs * ctx->cfg.n_agents;
   if (maps <= 0) return 0;
-  hipLaunchKernelGGL(k_plan, dim3(grid1(maps, 64)), dim3(64), 0, st, ctx->dcfg, rect, pos, comm, ws, global_maps, n_envs, agent_sel);
+  hipLaunchKernelGGL(k_plan, dim3(grid1(maps, 64)), dim3(64), 0, st, ctx->dcfg, rect, pos, comm, ws, global_maps, n_envs, agent_sel,
+                     ctx->backlog, ippm_backlog_words(ctx));
   IPPM_LAUNCH_CHECK("plan");
   return 0;
 }
@@ -606,13 +658,16 @@ extern "C" int ippm_plan_step(ippm_ctx* ctx, const int64_t* episode, int32_t* po
                               const int32_t* action_in, int32_t policy, uint8_t* mask, int32_t* action, int32_t* fault,
                               int32_t* rect_next, int32_t* work, int32_t n_envs, void* stream) {
   if (!ctx || !pos) { ippm_set_error("ippm_plan_step: null argument"); return -1; }
-  if ((flags & (IPPM_STEP_COMM | IPPM_STEP_GLOBAL | IPPM_STEP_MOVE)) == 0 || (flags & ~15)) { ippm_set_error("ippm_plan_step: bad flags"); return -1; }
+  if ((flags & (IPPM_STEP_COMM | IPPM_STEP_GLOBAL | IPPM_STEP_MOVE)) == 0 || (flags & ~31)) { ippm_set_error("ippm_plan_step: bad flags"); return -1; }
   // The form of the work list follows the CONTEXT, not the caller: ippm_fuse_step hands a list to the tile fusion exactly when
   // the context has the tile form, so that is the form built here --
   // IPPM_STEP_TILES is implied there and ignored elsewhere.  (Until round 5 the flag decided, and a caller who followed the
   // header -- plan without the flag, fuse with area sums -- got a list the tile fusion skipped: no fusion, rc 0.)
   if (ctx->tiles && work && (flags & (IPPM_STEP_COMM | IPPM_STEP_GLOBAL))) flags |= IPPM_STEP_TILES;
   else flags &= ~IPPM_STEP_TILES;
+  // clamp-only ops are deferred only where the tile fusion runs the plans and a backlog remembers what is owed (the caller leaves the flag
+  // out when it tracks area sums: those need every cell's stored value)
+  if (!(flags & IPPM_STEP_TILES) || !ctx->backlog) flags &= ~IPPM_STEP_DEFER_CLAMPS;
   if ((flags & IPPM_STEP_COMM) && (!comm || !rect || !ws)) { ippm_set_error("ippm_plan_step: comm/plan needs comm, rect, ws"); return -1; }
   if ((flags & IPPM_STEP_COMM) && !draws && !episode) { ippm_set_error("ippm_plan_step: Philox draws need the episode ids"); return -1; }
   if ((flags & IPPM_STEP_GLOBAL) && (!rect || !ws)) { ippm_set_error("ippm_plan_step: global plan needs rect, ws"); return -1; }
@@ -643,7 +698,8 @@ extern "C" int ippm_plan_step(ippm_ctx* ctx, const int64_t* episode, int32_t* po
                      ctx->dcfg, episode, comm_range, draws, comm, probs, action_in, mask, action, fault, rect_next, -1, plans ? work : nullptr,
                      ippm_fuse_wave_rows(ctx, n_envs), (flags & IPPM_STEP_TILES) ? ippm_tile_env_cap(ctx) : ippm_work_env_cap(ctx, n_envs),
                      ctx->n_active, ctx->slabs, ippm_slab_count(ctx),
-                     ctx->tl ? -1 : (tile_round ? 7 : 0));   // tile_build_map's round_mask
+                     ctx->tl ? -1 : (tile_round ? 7 : 0),    // tile_build_map's round_mask
+                     ctx->backlog, ippm_backlog_words(ctx));
   IPPM_LAUNCH_CHECK("plan_step");
   return 0;
 }

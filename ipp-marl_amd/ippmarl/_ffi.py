@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("IPPMARL_LIB", os.path.join(_HERE, "..", "lib", "libip
 WS_WORDS = 160
 FAULT_WORK_OVERFLOW = 0x40000000   # IPPM_FAULT_WORK_OVERFLOW (ippmarl.h): sticky bit of fault[e]
 FEAT, ACTOR_PLANES, CRITIC_PLANES = 11, 7, 12
-STEP_COMM, STEP_GLOBAL, STEP_MOVE, STEP_TILES = 1, 2, 4, 8   # ippm_plan_step flags
+STEP_COMM, STEP_GLOBAL, STEP_MOVE, STEP_TILES, STEP_DEFER_CLAMPS = 1, 2, 4, 8, 16   # ippm_plan_step flags
 CONV4X4_WGRAD_CHUNK = 256   # samples per partial sum of ippm_conv4x4_bf16_grad_weight (IPPM_CONV4X4_WGRAD_CHUNK)
 CONV5X5_WGRAD_CHUNK = 64   # samples per partial sum of ippm_conv5x5_bf16_grad_weight (IPPM_CONV5X5_WGRAD_CHUNK)
 HEAD_WGRAD_CHUNK = 64   # samples per partial sum of ippm_head_backward and the two losses (IPPM_HEAD_WGRAD_CHUNK)
@@ -76,6 +76,9 @@ PROTOTYPES = {
     "ippm_set_team_sizes": [P, P],
     "ippm_dirty_slab_words": [P, I32, P],
     "ippm_set_dirty_slabs": [P, P],
+    "ippm_clamp_backlog_words": [P, I32, P],
+    "ippm_set_clamp_backlog": [P, P],
+    "ippm_settle_clamps": [P, P, P, P, P, P, I32, P],
     "ippm_set_map_layout": [P, I32],
     "ippm_map_layout": [P, P],
     "ippm_map_layout_advice": [P, I32, P],
@@ -286,6 +289,7 @@ class Context:
         check(self.lib.ippm_read_counters(self.handle, C.byref(out), 1 if reset else 0, stream), "ippm_read_counters")
         res = {k: int(getattr(out, k)) for k, _ in IppmCounters._fields_ if k != "reserved"}
         res["work_list_rejects"] = int(out.reserved[0])   # fusion launches handed a work list of the other form (must stay 0)
+        res["settled_cells"] = int(out.reserved[1])       # cells whose value ippm_settle_clamps changed
         return res
 
 

@@ -106,7 +106,7 @@ class MapScores(NamedTuple):
 class VecEnv:
     def __init__(self, params: Dict, n_envs: int, device: str = "cuda:0", philox_seed: int = 3, terrain: str = "split",
                  track_area: bool = True, team_sizes=None, map_layout: str = "auto", layout_envs: Optional[int] = None,
-                 agent_rewards: Optional[bool] = None, terrain_library=None, library_augment: str = "d4"):
+                 agent_rewards: Optional[bool] = None, terrain_library=None, library_augment: str = "d4", defer_clamps: bool = True):
         if not torch.cuda.is_available():
             raise _ffi.IppmError("VecEnv needs an AMD GPU (HIP): there is no CPU path for the env step")
         self.params = params
@@ -160,6 +160,11 @@ class VecEnv:
         #   code   packed measurement codes (a nibble per 4-cell group)
         self._hot_shapes = (("local", (E, N, d.grid_x, d.grid_y), torch.float32), ("glob", (E, d.grid_x, d.grid_y), torch.float32),
                             ("code", (E, N, d.tile_bytes), torch.uint8), ("truth", (E, d.truth_bytes), torch.uint8))
+        # `local` / `glob` are properties over `_local` / `_glob`: reading them settles the clamp backlog first (below)
+        self.backlog = None
+        self._owing = False       # a plan step has deferred clips since the last settle: the backlog may be non-empty
+        self._observed = True     # the maps were looked at since the last plan step
+        self._plans = 0           # plan steps since the last reset
         self._place_hot()
         # Mixed team sizes in one batch (BASELINE config 5): env e flies team_sizes[e] <= n_agents UAVs and evolves exactly like a
         # run of the reference with that n_agents (its team size is a per-run parameter: coma_wrapper.py:25-26,
@@ -210,6 +215,18 @@ class VecEnv:
         yes = np.zeros(1, dtype=np.int32)
         self.ctx.call("ippm_tile_form", yes.ctypes.data)
         self._tile_form = bool(yes[0])   # the fusion runs in one-trip tile items (16-byte layout, prior 0.5), area sums tracked or not
+        # Clamp backlog (ippm_set_clamp_backlog): in the env-only form a plan step pushes no clamp-only ops -- what they
+        # would have clipped is remembered per map and clipped when `local` / `glob` are next READ (ippm_settle_clamps, from the properties).
+        # A rollout that looks at the maps rarely saves the fusion the cells that no message meets; a step that follows a look at the maps
+        # plans as before, so a caller that reads them at every step pays no extra launch.  Off with tracked area sums and per-agent
+        # rewards (both need every stored cell at every step) and once launches are captured into graphs.
+        self._defer = (bool(defer_clamps) and not track_area and d.vec == 4 and self._tile_form and not self.agent_rewards
+                       and d.budget + 4 <= 64)
+        if self._defer:
+            words = np.zeros(1, dtype=np.int64)
+            self.ctx.call("ippm_clamp_backlog_words", E, words.ctypes.data)
+            self.backlog = z(int(words[0]), dtype=torch.int32)
+            self.ctx.call("ippm_set_clamp_backlog", self._p(self.backlog))
         # 11x11 area sums of every map (slot N = global): the input of the K6 feature builders.  track_area=True: K3 / K4 /
         # K5 keep them up to date as they write maps (the batched training path); False: rebuilt by a streaming pass right
         # before the features are needed (env-only stepping never needs them; the single-env drop-in engine, whose maps
@@ -261,6 +278,35 @@ class VecEnv:
         for (name, shape, dt), (off, n) in zip(self._hot_shapes, spans):
             setattr(self, name, arena[off:off + n].view(dt).view(shape))
         self._boxes_valid = False          # the maps of another allocation: the next reset fills them whole
+
+    # `local` / `glob`: the belief maps as every reader must see them.  The step's own launches (plan, fusion, the closing K3, the resets) take
+    # `_local` / `_glob`; everything else -- read-back, features, scoring, the stand-alone entry points, other modules -- comes through here.
+    def _settle(self):
+        self._observed = True            # the next plan step pushes its clamp ops as ever (a caller that looks at every step never defers)
+        if self._owing:
+            self._owing = False
+            self.ctx.call("ippm_settle_clamps", self._p(self._local), self._p(self._glob), self._p(self.ws), self._p(self.rect),
+                          self._p(self.backlog), self.E, self.stream)
+
+    @property
+    def local(self) -> torch.Tensor:
+        self._settle()
+        return self._local
+
+    @local.setter
+    def local(self, t: torch.Tensor):
+        self._settle()
+        self._local = t
+
+    @property
+    def glob(self) -> torch.Tensor:
+        self._settle()
+        return self._glob
+
+    @glob.setter
+    def glob(self, t: torch.Tensor):
+        self._settle()
+        self._glob = t
 
     @property
     def profile(self) -> bool:
@@ -354,9 +400,11 @@ class VecEnv:
         one_pass = not self.track_area and d.vec == 4
         self.ctx.call("ippm_reset_episode", self._p(self.episode), self._p(self.pos),
                       self._p(self.truth) if truth is None and terrain == "split" else None,
-                      None if one_pass else self._p(self.local), None if one_pass else self._p(self.glob),
+                      None if one_pass else self._p(self._local), None if one_pass else self._p(self._glob),
                       self._p(self.split_pct), self._p(self.comm_range), self._p(self.ws), self._p(self.sums), self._area_arg,
                       self.E, self.stream)
+        self._owing = False       # (the reset empties the clamp backlog: the cells that were owed a clip are filled or sensed anew)
+        self._plans = 0
         if truth is not None:
             packed = d.pack_truth(torch.as_tensor(truth).cpu().numpy().reshape(self.E, d.grid_x, d.grid_y))
             self.truth.copy_(torch.from_numpy(packed).to(self.device))
@@ -383,8 +431,8 @@ class VecEnv:
         self._pending_t = None
         self._obs_t = None
         if one_pass:
-            self.ctx.call("ippm_reset_maps", self._p(self.episode), self._p(self.pos), self._p(self.truth), self._p(self.local),
-                          self._p(self.glob), self._p(flips), self._p(self.code), self._p(self.rect), self._p(self.ws),
+            self.ctx.call("ippm_reset_maps", self._p(self.episode), self._p(self.pos), self._p(self.truth), self._p(self._local),
+                          self._p(self._glob), self._p(flips), self._p(self.code), self._p(self.rect), self._p(self.ws),
                           0 if self._boxes_valid else 1, self.E, self.stream)
             self._boxes_valid = True
         else:
@@ -434,12 +482,13 @@ class VecEnv:
         """K3 at the current positions, called from outside the batched step (drop-in Agent / Mapping): the maps are then
         written without the plan kernel's knowledge, so the next reset fills them whole."""
         self._boxes_valid = False
+        self._settle()
         self._sense(stage, flips, agent, close_step)
 
     def _sense(self, stage: int, flips: Optional[torch.Tensor] = None, agent: int = -1, close_step: bool = False):
         """K3 at the current positions (stage 0 = start sensing, t+1 = sensing of step t).  ``close_step``: this is the K3
         that ends a batched step -- it takes the footprints K1 projected (rect_next) and completes the step's reward."""
-        self.ctx.call("ippm_sense_step", self._p(self.episode), self._p(self.pos), self._p(self.truth), self._p(self.local),
+        self.ctx.call("ippm_sense_step", self._p(self.episode), self._p(self.pos), self._p(self.truth), self._p(self._local),
                       self._p(flips), self._p(self.code), self._p(self.rect_next) if close_step else None, self._p(self.rect),
                       self._p(self.ws), self._area_arg, self._p(self.sums) if close_step else None,
                       self._p(self.reward) if close_step else None, stage, agent, self.E, self.stream)
@@ -459,13 +508,22 @@ class VecEnv:
     def _plan_step(self, t: int, flags: int, comm_draws=None, policy: int = 0, probs=None, actions=None):
         if self._tile_form and flags & (_ffi.STEP_COMM | _ffi.STEP_GLOBAL):
             flags |= _ffi.STEP_TILES   # the fusion takes the work list as one-trip tile items (16-byte layout, prior 0.5)
+            if self._defer:
+                # the backlog's list of unclamped rectangles holds one episode's steps: past them, settle and plan as ever
+                self._plans += 1
+                if self._plans > self.d.budget + 1:
+                    self._settle()
+                elif not self._observed:
+                    flags |= _ffi.STEP_DEFER_CLAMPS
+                    self._owing = True
+                self._observed = False
         self.ctx.call("ippm_plan_step", self._p(self.episode), self._p(self.pos), self._p(self.comm_range), self._p(comm_draws),
                       self._p(self.comm), self._p(self.rect), self._p(self.ws), t, flags, self._p(probs), self._p(actions), policy,
                       self._p(self.mask), self._p(self.action), self._p(self.fault), self._p(self.rect_next), self._p(self.work), self.E,
                       self.stream)
 
     def _fuse_step(self):
-        self.ctx.call("ippm_fuse_step", self._p(self.local), self._p(self.glob), self._p(self.code), self._p(self.ws),
+        self.ctx.call("ippm_fuse_step", self._p(self._local), self._p(self._glob), self._p(self.code), self._p(self.ws),
                       self._p(self.sums), self._area_arg, self._p(self.work), self.E, self.stream)
 
     def _actor_features(self, t: int):
@@ -615,6 +673,8 @@ class VecEnv:
         per-step arguments t / stage are baked in, all arrays are fixed device buffers).  The sensing kernel K3 stays an
         ordinary launch so that callers can bracket it with events."""
         graphs = []
+        self._settle()
+        self._defer = False      # (a recorded plan step cannot follow what the host has looked at: replayed steps plan as ever)
         torch.cuda.synchronize(self.device)
         saved = {k: getattr(self, k).clone() for k in ("local", "glob", "ws", "sums", "pos", "comm", "mask", "action", "fault", "reward",
                                                        "area", "rect_next")}
@@ -799,7 +859,7 @@ class SplitVecEnv:
 
     def __init__(self, params: Dict, n_envs: int, parts: int = 2, device: str = "cuda:0", philox_seed: int = 3, terrain: str = "split",
                  track_area: bool = False, team_sizes=None, map_layout: str = "auto", agent_rewards: Optional[bool] = None,
-                 terrain_library=None, library_augment: str = "d4"):
+                 terrain_library=None, library_augment: str = "d4", defer_clamps: bool = True):
         if parts < 1 or n_envs < parts:
             raise ValueError("SplitVecEnv: 1 <= parts <= n_envs")
         self.device = torch.device(device)
@@ -817,7 +877,8 @@ class SplitVecEnv:
             with torch.cuda.stream(self.streams[k]):
                 self.parts.append(VecEnv(params, n, device=device, philox_seed=philox_seed, terrain=terrain, track_area=track_area,
                                          team_sizes=None if ts is None else ts[off:off + n], map_layout=map_layout, layout_envs=int(n_envs),
-                                         agent_rewards=agent_rewards, terrain_library=terrain_library, library_augment=library_augment))
+                                         agent_rewards=agent_rewards, terrain_library=terrain_library, library_augment=library_augment,
+                                         defer_clamps=defer_clamps))
         self.E = int(n_envs)
         self.d = self.parts[0].d
         self.tiled = self.parts[0].tiled
@@ -977,8 +1038,10 @@ class SplitVecEnv:
         return rows_view(maps, self.tiled)
 
     def _cat(self, name):
+        # (each part's tensor is taken on the part's own stream: reading `local` / `glob` may launch that part's ippm_settle_clamps)
+        vals = [getattr(env, name) for env, _ in self._each()]
         self.join()
-        return torch.cat([getattr(env, name) for env in self.parts], dim=0)
+        return torch.cat(vals, dim=0)
 
     pos = property(lambda self: self._cat("pos"))
     local = property(lambda self: self._cat("local"))
